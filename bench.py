@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 512x512 triplane-head inference render at max_steps = 192 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without WORLD_SIZE in the environment: this process spawns `python -m torch.distributed.run --nproc-per-node N` on itself
 BEFORE touching the GPU and exits with the children's code; under torch.distributed.run it is one rank per GPU over RCCL.
@@ -133,11 +133,46 @@ def parse_args():
                          "needs: a stale cache line or a torn hand-off shows up as a mismatch count in `verify_frames`)")
     ap.add_argument("--gather", default="f32", choices=["f32", "rgb24"],
                     help="what the per-step all-gather moves: f32 RGB tiles, or the video pipe's RGB24 quantised on device (4x fewer bytes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the headline path returned in its last timed step as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all; beyond that a fixed seeded sample of rows, with DIR/<name>_rows.npy): the "
+                         "renderer's per-ray outputs and, for N > 1, the gathered frame.  Inputs are seeded: same arguments, same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_side_legs:
         args.no_train = args.no_cpu_baseline = args.no_grid_roofline = args.no_fat_schedule = args.no_fp16_leg = True
         args.no_occupancy = args.no_dense192 = args.no_cfg5 = True
     return args
+
+
+DUMP_BYTES = 64 << 20
+# what TriplaneRenderer.render hands its caller, minus `state` (the kernels' device-side status and scheduling block, not an output)
+DUMP_KEYS = ("image", "image_raw", "weights_sum", "depth", "amb_aud_sum", "amb_eye_sum", "uncertainty_sum", "nears", "fars", "image_rgb24")
+
+
+def snapshot_outputs(out, frame):
+    """host float32 copies of the headline step's outputs (taken right after the timed region, before later legs reuse the buffers)"""
+    arrays = {k: out[k].float().cpu().numpy() for k in DUMP_KEYS if k in out}
+    if frame is not None:
+        arrays["frame"] = frame.float().cpu().numpy()
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy for every array; if they exceed DUMP_BYTES together, the same fraction of each array's rows, drawn with a fixed
+    seed, plus DIR/<name>_rows.npy (float64 row indices) -- identical runs pick identical rows"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float32) for k, a in arrays.items()}
+    cost = sum(a.shape[0] * (a[:1].nbytes + 8) for a in arrays.values())
+    frac = 1.0 if sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES - (64 << 10) else (DUMP_BYTES - (64 << 10)) / cost
+    for name, a in sorted(arrays.items()):
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], int(a.shape[0] * frac), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step: {len(arrays)} arrays in {path}" + (f" (a seeded {frac:.3f} of the rows)" if frac < 1.0 else ""))
 
 
 def main():
@@ -189,6 +224,10 @@ def main():
     job = make_job(args.shard, args.tiles, shard_of=args.shard_of)
     dt, head_ms, out, tiles = timed(job, args.steps, args.warmup, world, device)
     dt_own = job.dt_own
+    if args.dump_outputs and rank == 0:
+        if world > 1:
+            job.sf.wait()
+        dump_outputs(snapshot_outputs(out, job.sf.assemble(tiles) if world > 1 else None), args.dump_outputs)
     samples_per_step, iters_per_frame, rows_per_step = frame_stats(out, world, device)
     log(f"headline: {dt / args.steps * 1e3:.3f} ms/step")
     frames_per_step = world if (world > 1 and args.shard == "clip") else 1

@@ -59,3 +59,28 @@ def test_bench_prints_through_the_contract_module():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert "json.dumps(compact(result, detail))" in src and "print(json.dumps(result))" not in src
     assert src.count("print(") <= 3, "bench.py prints: the train-only object, the contract line -- nothing else on stdout"
+
+
+def test_dump_outputs_stays_within_the_budget_and_repeats(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; arrays over the byte budget are cut to the same seeded rows on every run"""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    arrays = {"image": rng.random((1 << 18, 3), dtype=np.float32), "depth": rng.random(1 << 18, dtype=np.float32),
+              "image_rgb24": rng.integers(0, 256, (1 << 18, 3)).astype(np.uint8)}
+    small = {"depth": arrays["depth"][:1000]}
+    bench.dump_outputs(small, str(tmp_path / "whole"))
+    assert sorted(os.listdir(tmp_path / "whole")) == ["depth.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "depth.npy"), small["depth"])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 << 20)
+    for run in ("a", "b"):
+        bench.dump_outputs(arrays, str(tmp_path / run))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "image.npy" in files and "image_rows.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 2 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    rows = np.load(tmp_path / "a" / "image_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), arrays["image"][rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "image_rgb24.npy"), arrays["image_rgb24"][rows].astype(np.float32))

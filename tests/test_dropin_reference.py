@@ -1,7 +1,10 @@
-"""Drop-in check against the reference's own, unmodified caller code.  Runs only where /root/reference exists (the
-build container; the GPU box has no reference tree, and these tests need no GPU): with lzzx_nerf_amd/dropin in front
-of sys.path the reference's nerf_triplane.network.NeRFNetwork must construct on top of this repo's encoder modules
-and expose the same state_dict contract."""
+"""Drop-in check against the reference's own, unmodified caller code, held to a record of it: tests/golden/reference_dropin.json holds
+every get_encoder call the reference's nerf_triplane.network.NeRFNetwork constructor makes (with lzzx_nerf_amd/dropin in front of
+sys.path), the classes and output_dims it received, and the state_dict contract of the network it built (generated in the build
+container by tests/golden/make_golden_dropin.py).  Here, with the drop-in directory in front of sys.path, the reference's import names
+must resolve to the drop-in modules, and the recorded calls replayed on them must return the same modules -- class, output_dim, grid type
+and state_dict entries -- that the reference's network was built from.  No GPU needed."""
+import json
 import os
 import subprocess
 import sys
@@ -10,42 +13,51 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "nerf_triplane")), reason="reference tree not present")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_dropin.json")
 
 SCRIPT = textwrap.dedent("""
-    import sys, types
-    sys.path.insert(0, %(dropin)r); sys.path.insert(1, %(root)r); sys.path.insert(2, %(ref)r)
-    for name in ("lpips", "trimesh", "mcubes", "cv2", "tensorboardX", "torch_ema", "imageio", "pydub", "numba"):
-        try: __import__(name)
-        except Exception: sys.modules[name] = types.ModuleType(name)   # absent third-party packages off the hot path
+    import json, sys
+    sys.path.insert(0, %(dropin)r); sys.path.insert(1, %(root)r)
     import encoding, raymarching, gridencoder, shencoder, freqencoder
-    assert encoding.__file__.startswith(%(dropin)r) and raymarching.__file__.startswith(%(dropin)r)
-    from nerf_triplane.network import NeRFNetwork            # reference source, unmodified
-    import lzzx_nerf_amd.gridencoder as G, lzzx_nerf_amd.shencoder as S, lzzx_nerf_amd.freqencoder as F
-    class Opt:
-        bound=1; min_near=0.05; density_thresh=10; density_thresh_torso=0.01; exp_eye=True; test_train=False
-        smooth_lips=False; torso=%(torso)s; cuda_ray=True; ind_num=10; ind_dim=4; ind_dim_torso=8; train_camera=False
-        emb=False; asr_model='deepspeech'; att=2; unc_loss=1; torso_shrink=0.8
-    net = NeRFNetwork(Opt())
-    assert type(net.encoder_xy) is G.GridEncoder and type(net.encoder_dir) is S.SHEncoder
-    assert net.in_dim == 36 and net.in_dim_dir == 16
-    sd = net.state_dict()
-    assert tuple(sd['encoder_xy.embeddings'].shape) == (163584, 1) and str(sd['encoder_yz.offsets'].dtype) == 'torch.int32'
-    assert tuple(sd['sigma_net.net.0.weight'].shape) == (64, 69) and tuple(sd['density_bitfield'].shape) == (262144,)
-    if %(torso)s:
-        assert type(net.torso_deform_encoder) is F.FreqEncoder and net.torso_deform_in_dim == 34
-        assert type(net.torso_encoder) is G.GridEncoder and net.torso_encoder.gridtype == 'tiled' and net.torso_in_dim == 32
-    # the fused head consumes this state_dict as is (construction + packing need a GPU, so only the key contract here)
-    from lzzx_nerf_amd import head
-    assert all(k in sd for k in head._W_KEYS)
+    assert all(m.__file__.startswith(%(dropin)r) for m in (encoding, raymarching, gridencoder, shencoder, freqencoder))
+    rec = json.load(open(%(fixture)r))[%(case)r]
+    sd = rec["state_dict"]
+    for c in rec["get_encoder_calls"]:
+        enc, dim = encoding.get_encoder(*c["args"], **c["kwargs"])
+        assert type(enc).__module__ + "." + type(enc).__qualname__ == c["type"], (c["attr"], type(enc))
+        assert dim == c["output_dim"] == enc.output_dim, (c["attr"], dim)
+        assert getattr(enc, "gridtype", None) == c.get("gridtype"), c["attr"]
+        mine = {k: [list(v.shape), str(v.dtype)] for k, v in enc.state_dict().items()}
+        want = {k[len(c["attr"]) + 1:]: v for k, v in sd.items() if k.startswith(c["attr"] + ".")}
+        assert mine == want, (c["attr"], mine, want)
     print('DROPIN_OK', len(sd))
 """)
 
 
+@pytest.fixture(scope="module")
+def record():
+    return json.load(open(FIXTURE))
+
+
 @pytest.mark.parametrize("torso", [False, True])
-def test_reference_network_constructs_on_dropin(torso):
-    code = SCRIPT % dict(dropin=os.path.join(ROOT, "lzzx_nerf_amd", "dropin"), root=ROOT, ref=REF, torso=torso)
+def test_reference_network_constructs_on_dropin(torso, record):
+    case = "torso=%s" % torso
+    rec = record[case]
+    sd, dims = rec["state_dict"], rec["dims"]
+    attrs = {c["attr"]: c for c in rec["get_encoder_calls"]}
+    # what the reference built on the drop-in modules
+    assert attrs["encoder_xy"]["type"].endswith("GridEncoder") and attrs["encoder_dir"]["type"].endswith("SHEncoder")
+    assert dims["in_dim"] == 36 and dims["in_dim_dir"] == 16
+    assert sd["encoder_xy.embeddings"] == [[163584, 1], "torch.float32"] and sd["encoder_yz.offsets"][1] == "torch.int32"
+    assert sd["sigma_net.net.0.weight"][0] == [64, 69] and sd["density_bitfield"][0] == [262144]
+    if torso:
+        assert attrs["torso_deform_encoder"]["type"].endswith("FreqEncoder") and dims["torso_deform_in_dim"] == 34
+        assert attrs["torso_encoder"]["type"].endswith("GridEncoder") and attrs["torso_encoder"]["gridtype"] == "tiled"
+        assert dims["torso_in_dim"] == 32
+    # the fused head consumes this state_dict as is (construction + packing need a GPU, so only the key contract here)
+    from lzzx_nerf_amd import head
+    assert all(k in sd for k in head._W_KEYS)
+    # ... and the drop-in modules, imported under the reference's names, still answer the recorded calls with the same modules
+    code = SCRIPT % dict(dropin=os.path.join(ROOT, "lzzx_nerf_amd", "dropin"), root=ROOT, fixture=FIXTURE, case=case)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "DROPIN_OK" in r.stdout, r.stderr[-3000:]
