@@ -653,7 +653,10 @@ int lz_loop_run(const lz_frame* f, uint32_t parity, uint32_t n_iterations, lz_ti
  *   cap_mode 0 (LZ_FRAME_CAP_PER_RAY): a ray alive at the cap stops at ceil(max_steps / S) * S samples, S = steps_per_pass: the loop under
  *     the schedule n_step = S.  No histogram, no second phase, no exchange between ranks -- and not the reference's pixels on rays that
  *     reach the cap (every ray that leaves the box or falls under T_thresh before max_steps is unaffected).
- * All pointers are device pointers; the caller owns every buffer.  state words after the call (stream order):
+ * All pointers are device pointers; the caller owns every buffer.  Besides them the f32 heads (precision 0 and 2) use 256 B per ray of
+ * library-internal memory for the call's duration -- the per-ray SH partial of colour_net.0 (lz_k_frame_c1sh) -- taken stream-ordered
+ * from a pool per device that the library keeps (hipMallocFromPoolAsync / hipFreeAsync on `stream`, release threshold: never; 67 MB
+ * for a 512^2 frame): no host synchronisation, nothing shared between calls or streams.  state words after the call (stream order):
  *   [1] rays that had at least one sample, [3] 1, [5] composited samples (with ray_counts under cap_mode 1: marched samples = the sum of
  *   ray_counts), [6] 1, [72] sample rows evaluated by the head (16 per slice) -- words 3 / 5 / 6 / 72 as in lz_loop_state /
  *   LZ_LOOP_STAT_ROWS; cap_mode 1 adds [9] rays phase 2 continued, [10] C_eff, [11] iterations of the reference's loop. */

@@ -40,6 +40,8 @@
 // cap_mode 0 keeps the per-ray cap ceil(max_steps / S) * S (no histogram, no second phase).
 #include <stdlib.h>
 
+#include <mutex>
+
 #include "lz_march.h"
 #include "lz_head_slice.h"
 #include "lz_head_f16_slice.h"
@@ -86,6 +88,7 @@ struct LzFrameK {
     int* cap_ws;          // [0 .. max_steps] histogram of L (what ranks all-reduce), then the schedule tables (lz_k_frame_schedule)
     uint32_t cap_mode, phase2, N_total;
     LzMarchFrame mf;      // the march's frame-wide quotients (lz_march_frame on the host)
+    float* c1sh;          // f32 heads: [N][LZ_C1_SH_FLOATS] per-ray SH partial of colour_net.0 (lz_k_frame_c1sh; library-internal, see lzf_c1sh_alloc)
 };
 
 // The per-ray OUTPUT side of LzFrameK (eleven pointers, the background, the cap's buffers) is touched once per ray, when it leaves its slot.
@@ -240,16 +243,40 @@ __global__ void __launch_bounds__(LZF_PREP_WG) lz_k_frame_scatter(LzFrameK F) {
     if (key > 0) F.order[start[key] + lbase[key] + lrank] = (int)n;
 }
 
+// ---- pass 2b (f32 heads): the per-ray SH partial of colour_net.0 for the rays of the queue -------------------------------------------
+// One wave per 16 queue entries: SH(4) of the ray's direction (the lz_sh_eval call the stand-alone head makes per sample), then k-steps
+// 0 .. 3 of colour_net.0 on the same fragments the slice would use (lz_head_slice.h: lz_c1_sh_partial), 64 f32 per ray into F.c1sh.
+// Phase 1 covers order[0 .. Q_SIZE), lz_frame_finish's phase 2 (a separate call) order[0 .. P_SIZE): the rays parked at the cap.
+#define LZF_C1SH_WG 256
+__global__ void __launch_bounds__(LZF_C1SH_WG) lz_k_frame_c1sh(const float* __restrict__ packed, LzFrameK F) {
+    const int lane = threadIdx.x & 63, s = lane & 15, q = lane >> 4;
+    const int n_queue = F.state[F.phase2 ? LZF_P_SIZE : LZF_Q_SIZE];
+    const int tile = blockIdx.x * (LZF_C1SH_WG / 64) + (threadIdx.x >> 6);
+    if (tile * 16 >= n_queue) return;                                  // wave-uniform: the MFMAs below need the whole wave
+    const int idx = tile * 16 + s;
+    const int ray = idx < n_queue ? F.order[idx] : -1;                 // a partial tile: columns of no ray are computed and dropped
+    const float* d = F.rays_d + (size_t)(ray < 0 ? 0 : ray) * 3;
+    auto sh = lz_sh_from_dir([d](float& x, float& y, float& z) { x = d[0]; y = d[1]; z = d[2]; });
+    lz_f4 acc[4][1];
+    lz_c1_sh_partial(packed, lane, sh, acc);
+    if (ray >= 0) {
+        float* row = F.c1sh + (size_t)ray * LZ_C1_SH_FLOATS + 16 * q;
+#pragma unroll
+        for (int ft = 0; ft < 4; ft++) *reinterpret_cast<lz_f4*>(row + 4 * ft) = acc[ft][0];
+    }
+}
+
 // ---- pass 3: the persistent kernel --------------------------------------------------------------------------------------------
 // slot state in LDS, per wave [field][16]
 enum { SF_RAY = 0, SF_T, SF_FAR, SF_DT, SF_WS, SF_D, SF_R, SF_G, SF_B, SF_A0, SF_A1, SF_U, SF_CNT,
-       SF_SH };                     // SH(4) of the ray's direction, evaluated once per ray at refill (the head needs it per sample): 16 f32
-                                    // words, or 8 words of packed halves for the f16 head.  The staging fields behind it depend on the
+       SF_SH };                     // f16 head: SH(4) of the ray's direction, evaluated once per ray at refill (the head needs it per sample),
+                                    // 8 words of packed halves.  The f32 heads keep nothing here: they read the per-ray SH partial of
+                                    // colour_net.0 (lz_k_frame_c1sh) from global memory instead.  The staging fields behind it depend on the
                                     // kernel's arrangement: LzfFields
 // fields behind SF_SH.  S > 1: per-SAMPLE staging (march -> head: X Y Z TS; head -> composite: OSIG .. OU) and the per-ray pass counter IT;
 // S == 1 with several slot rows: only the parked head outputs; one row: nothing
 template <int PREC, int S, int ROWS> struct LzfFields {
-    static constexpr int SH_WORDS = PREC == 1 ? 8 : 16;
+    static constexpr int SH_WORDS = PREC == 1 ? 8 : 0;
     static constexpr int ST = SF_SH + SH_WORDS;
     static constexpr int X = ST, Y = ST + 1, Z = ST + 2, TS = ST + 3;                       // S > 1 only
     static constexpr int OSIG = S > 1 ? ST + 4 : ST, OR = OSIG + 1, OG = OSIG + 2, OB = OSIG + 3, OA0 = OSIG + 4, OA1 = OSIG + 5, OU = OSIG + 6;
@@ -262,14 +289,6 @@ template <int PREC, int S, int ROWS> struct LzfFields {
     static constexpr int COUNT = RD + 3 + (GEO ? 6 : 0);
 };
 
-// SH(4) of the slot's ray from LDS: component k of the ray whose state sits at slot `ls` (fields are `ns` slots wide)
-struct LzShFromSlot {
-    const float* slot;
-    int ls, ns;
-    __device__ __forceinline__ void prepare() const {}
-    __device__ __forceinline__ float comp_iq(int i, int q) const { return slot[(SF_SH + 4 * i + q) * ns + ls]; }
-    __device__ __forceinline__ float comp_qj(int q, int j) const { return slot[(SF_SH + 4 * q + j) * ns + ls]; }
-};
 // the f16 head consumes SH as halves: the slot keeps them packed (components 2 k, 2 k + 1 in word k of 8), converted once per ray
 struct LzShFromSlot16 {
     const float* slot;
@@ -280,11 +299,10 @@ __device__ __forceinline__ void w_sh_pk(const LzShFromSlot16& f, int h, uint32_t
 #pragma unroll
     for (int k = 0; k < 4; k++) w[k] = __float_as_uint(f.slot[(SF_SH + 4 * h + k) * f.ns + f.ls]);
 }
-// evaluated by the lane that takes the ray (the same lz_sh_eval call on the same direction as the stand-alone head makes per sample)
+// per-ray direction terms, stored by the lane that takes the ray; the f16 head's SH(4) with them (the same lz_sh_eval call on the same
+// direction as the stand-alone head makes per sample)
 template <int PREC, bool GEO = false>
 __device__ __forceinline__ void lzf_store_sh(const float* __restrict__ ro, const float* __restrict__ d, float* slot, int s, int ns, int rd_field) {
-    float o[16];
-    lz_sh_eval(d[0], d[1], d[2], 4, o, nullptr, nullptr, nullptr);
     slot[rd_field * ns + s] = 1 / d[0];              // LzMarch's reciprocals: per ray here, not per pass
     slot[(rd_field + 1) * ns + s] = 1 / d[1];
     slot[(rd_field + 2) * ns + s] = 1 / d[2];
@@ -296,11 +314,10 @@ __device__ __forceinline__ void lzf_store_sh(const float* __restrict__ ro, const
         }
     }
     if constexpr (PREC == 1) {
+        float o[16];
+        lz_sh_eval(d[0], d[1], d[2], 4, o, nullptr, nullptr, nullptr);
 #pragma unroll
         for (int k = 0; k < 8; k++) slot[(SF_SH + k) * ns + s] = __uint_as_float(h_cvt2(o[2 * k], o[2 * k + 1], false));
-    } else {
-#pragma unroll
-        for (int k = 0; k < 16; k++) slot[(SF_SH + k) * ns + s] = o[k];
     }
 }
 
@@ -345,9 +362,14 @@ __device__ __forceinline__ void lzf_ray_end(const LzfOut& O, bool ph2, int ray, 
 
 template <int PREC> struct LzfHead;
 template <> struct LzfHead<0> {
-    using Args = LzHeadArgs; using Ctx = LzHeadCtx; using Out = LzHeadOut; using ShSlot = LzShFromSlot;
+    using Args = LzHeadArgs; using Ctx = LzHeadCtx; using Out = LzHeadOut;
     static constexpr int LDS_WORDS = LzHeadLds<false>::FLOATS;
     __device__ static __forceinline__ void stage(const Args& P, float* lds, int q, Ctx& c) { lz_head_stage<false>(P, lds, LZF_WG, q, c); }
+    // the SH source of a slice: the per-ray partial of colour_net.0 of the ray at slot `ls` (lz_k_frame_c1sh), this lane's quarter
+    __device__ static __forceinline__ LzShPartial sh(const LzfOut& O, const float* slot, int ls, int ns, int q) {
+        const int ray = reinterpret_cast<const int*>(slot)[SF_RAY * ns + ls];
+        return LzShPartial{ray >= 0 ? LZF_OUT(O, c1sh) + (size_t)ray * LZ_C1_SH_FLOATS + 16 * q : nullptr};
+    }
     template <typename ShFn>
     __device__ static __forceinline__ void slice(const Ctx& c, int lane, float x, float y, float z, ShFn f, Out& o) {
         lz_head_slice<false, false, true, true>(c, lane, x, y, z, f, o);
@@ -360,9 +382,10 @@ template <> struct LzfHead<2> : LzfHead<0> {   // f32 with the geo projection fo
     }
 };
 template <> struct LzfHead<1> {   // f16: 32-sample slices on v_mfma_f32_32x32x16_f16 (lz_head_f16w_slice.h)
-    using Args = LzHead16Args; using Ctx = LzHead16Ctx; using Out = LzHead16wOut; using ShSlot = LzShFromSlot16;
+    using Args = LzHead16Args; using Ctx = LzHead16Ctx; using Out = LzHead16wOut;
     static constexpr int LDS_WORDS = LZ_HEAD16W_LDS_H8 * 4;
     __device__ static __forceinline__ void stage(const Args& P, float* lds, int, Ctx& c) { lz_head16w_stage(P, reinterpret_cast<lz_h8*>(lds), LZF_WG, c); }
+    __device__ static __forceinline__ LzShFromSlot16 sh(const LzfOut&, const float* slot, int ls, int ns, int) { return LzShFromSlot16{slot, ls, ns}; }
     template <typename ShFn>
     __device__ static __forceinline__ void slice(const Ctx& c, int lane, float x, float y, float z, ShFn f, Out& o) {
         lz_head16w_slice<true, LZ_F16W_PRIO != 0>(c, lane, x, y, z, f, o);
@@ -569,7 +592,7 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
             const bool live = sloti[SF_RAY * NS + lead] >= 0 && j < lkk;
             const float px = live ? slot[SF_X * NS + s] : 0.0f, py = live ? slot[SF_Y * NS + s] : 0.0f, pz = live ? slot[SF_Z * NS + s] : 0.0f;
             typename HD::Out o;
-            HD::slice(ctx, lane, px, py, pz, typename HD::ShSlot{slot, lead, NS}, o);
+            HD::slice(ctx, lane, px, py, pz, HD::sh(OUT, slot, lead, NS, q), o);
             my_slices += ROWS;
             if constexpr (PREC == 1) {
                 // the f16 head leaves a sample's four transcendentals two per lane (LzHead16wOut: rgb[0], rgb[2] on lane half 0; rgb[1], sigma on
@@ -715,7 +738,7 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
                     return __uint_as_float(r[0]);
                 };
                 const float px = lo2(x), py = lo2(y), pz = lo2(z);
-                HD::slice(ctx, lane, px, py, pz, typename HD::ShSlot{slot, rs, NS}, o);
+                HD::slice(ctx, lane, px, py, pz, HD::sh(OUT, slot, rs, NS, q), o);
                 my_slices += 2;
                 slot[(SF_OR + hh) * NS + rs] = o.a;
                 slot[(hh ? SF_OSIG : SF_OB) * NS + rs] = o.b;
@@ -726,7 +749,7 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
                     if (ROWS > 1 && !((have_mask >> (16 * row)) & 0xffffull)) continue;   // no sample in this row
                     const int rs = 16 * row + s;                   // the slot whose sample this lane works on
                     const float px = __shfl(x, rs, 64), py = __shfl(y, rs, 64), pz = __shfl(z, rs, 64);
-                    HD::slice(ctx, lane, px, py, pz, typename HD::ShSlot{slot, rs, NS}, o);
+                    HD::slice(ctx, lane, px, py, pz, HD::sh(OUT, slot, rs, NS, q), o);
                     my_slices++;
                     if (ROWS > 1 && q == 0) {   // park the row's outputs for the compositing below (lanes q == 0 hold valid bits)
                         slot[SF_OSIG * NS + rs] = o.sigma;
@@ -1096,6 +1119,50 @@ static int lzf_fill(const lz_frame_fused* f, LzFrameK& K) {
     K.occ = f->occupied_aabb; K.t_end = f->t_end;
     K.ray_last = f->ray_last; K.cap_ws = f->cap_ws; K.cap_mode = f->cap_mode; K.phase2 = 0; K.N_total = f->N_total;
     K.mf = lz_march_frame(f->bound, f->max_steps, f->C, f->H);
+    K.c1sh = nullptr;
+    return LZ_OK;
+}
+
+// The per-ray SH partials of the f32 heads (256 B per ray: 67 MB for a 512^2 frame) fit neither in LDS nor in any scratch buffer of
+// lz_frame_fused, and the ABI stays as it is: a library-internal, stream-ordered allocation per call (hipMallocFromPoolAsync /
+// hipFreeAsync on the call's stream) from a pool per device that keeps its memory (release threshold: never), so after the first frame
+// an allocation is a bookkeeping step -- no host synchronisation inside the frame, and frames on different streams never share a buffer.
+static hipMemPool_t lzf_c1sh_pool() {
+    static std::mutex mu;
+    static hipMemPool_t pools[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!pools[dev]) {
+        hipMemPoolProps props;
+        memset(&props, 0, sizeof(props));
+        props.allocType = hipMemAllocationTypePinned;
+        props.location.type = hipMemLocationTypeDevice;
+        props.location.id = dev;
+        hipMemPool_t pool = nullptr;
+        if (hipMemPoolCreate(&pool, &props) != hipSuccess) return nullptr;
+        uint64_t keep = UINT64_MAX;
+        (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
+        pools[dev] = pool;
+    }
+    return pools[dev];
+}
+struct LzfC1Sh {                    // owns one call's partials; returned to the pool in stream order behind the call's last launch
+    float* p = nullptr;
+    hipStream_t st = nullptr;
+    ~LzfC1Sh() { if (p) (void)hipFreeAsync(p, st); }
+};
+// f32 heads: allocate the partials of f's N rays and launch lz_k_frame_c1sh over the queue of K's phase (behind the kernels that fill it)
+static int lzf_c1sh_prepare(const lz_frame_fused* f, LzFrameK& K, LzfC1Sh& buf, hipStream_t st) {
+    if (f->head.precision == 1) return LZ_OK;
+    hipMemPool_t pool = lzf_c1sh_pool();
+    LZ_REQUIRE(pool, (int)hipErrorNotSupported, "frame_render: no memory pool for the SH partials");
+    const hipError_t e = hipMallocFromPoolAsync(reinterpret_cast<void**>(&buf.p), (size_t)f->N * LZ_C1_SH_FLOATS * sizeof(float), pool, st);
+    if (e != hipSuccess) { buf.p = nullptr; lz_set_error("frame_render: SH partials: %s", hipGetErrorString(e)); return (int)e; }
+    buf.st = st;
+    K.c1sh = buf.p;
+    hipLaunchKernelGGL(lz_k_frame_c1sh, dim3(lz_div_up(f->N, 16 * (LZF_C1SH_WG / 64))), dim3(LZF_C1SH_WG), 0, st,
+                       reinterpret_cast<const float*>(f->head.packed), K);
     return LZ_OK;
 }
 
@@ -1183,22 +1250,31 @@ static int lzf_launch_persistent(const lz_frame_fused* f, const LzFrameK& K, hip
     return LZ_OK;
 }
 
+// phase 2 and the counts.  c1sh: phase 1's SH partials when lz_frame_render calls this itself (every ray phase 2 continues was in phase 1's
+// queue); null from a separate lz_frame_finish call, which computes its own for the rays parked at the cap (nothing is kept between calls)
+static int lzf_finish(const lz_frame_fused* f, hipStream_t st, float* c1sh) {
+    LzFrameK K;
+    lzf_fill(f, K);
+    if (f->defer_finish) hipLaunchKernelGGL(lz_k_frame_schedule, dim3(1), dim3(256), LZF_SCHED_LDS_INTS(f->max_steps) * sizeof(int), st, K);
+    K.phase2 = 1;
+    LzfC1Sh own;
+    int rc = LZ_OK;
+    if (c1sh) K.c1sh = c1sh;
+    else if ((rc = lzf_c1sh_prepare(f, K, own, st)) != LZ_OK) return rc;
+    rc = lzf_launch_persistent(f, K, st);
+    if (rc != LZ_OK) return rc;
+    if (f->ray_counts) hipLaunchKernelGGL(lz_k_frame_counts, dim3(lz_div_up(f->N, 256)), dim3(256), 0, st, K);
+    LZ_CHECK_LAUNCH("frame_finish");
+    return LZ_OK;
+}
+
 extern "C" int lz_frame_finish(const lz_frame_fused* f, lz_stream_t stream) {
     LZ_REQUIRE(f, LZ_ERR_BAD_ARGUMENT, "frame_finish: null");
     LZ_REQUIRE(f->cap_mode == LZ_FRAME_CAP_REFERENCE, LZ_ERR_BAD_ARGUMENT, "frame_finish: only after lz_frame_render with cap_mode 1");
     if (f->N == 0 && f->state) return LZ_OK;       // an empty tile (see lz_frame_render)
     int rc = lzf_check(f, "frame_finish");
     if (rc != LZ_OK) return rc;
-    hipStream_t st = lz_st(stream);
-    LzFrameK K;
-    lzf_fill(f, K);
-    if (f->defer_finish) hipLaunchKernelGGL(lz_k_frame_schedule, dim3(1), dim3(256), LZF_SCHED_LDS_INTS(f->max_steps) * sizeof(int), st, K);
-    K.phase2 = 1;
-    rc = lzf_launch_persistent(f, K, st);
-    if (rc != LZ_OK) return rc;
-    if (f->ray_counts) hipLaunchKernelGGL(lz_k_frame_counts, dim3(lz_div_up(f->N, 256)), dim3(256), 0, st, K);
-    LZ_CHECK_LAUNCH("frame_finish");
-    return LZ_OK;
+    return lzf_finish(f, lz_st(stream), nullptr);
 }
 
 extern "C" int lz_frame_render(const lz_frame_fused* f, lz_timing* timing, lz_stream_t stream) {
@@ -1225,6 +1301,9 @@ extern "C" int lz_frame_render(const lz_frame_fused* f, lz_timing* timing, lz_st
     const uint32_t nb = lz_div_up(f->N, LZF_PREP_WG);
     hipLaunchKernelGGL(lz_k_frame_prepare, dim3(nb), dim3(LZF_PREP_WG), 0, st, K);
     hipLaunchKernelGGL(lz_k_frame_scatter, dim3(nb), dim3(LZF_PREP_WG), 0, st, K);
+    LzfC1Sh c1sh;                                           // f32 heads: the per-ray SH partials (freed in stream order on return)
+    rc = lzf_c1sh_prepare(f, K, c1sh, st);
+    if (rc != LZ_OK) return rc;
     if (timing) (void)lz_timing_mark(timing, 0, stream);    // the event pair brackets the persistent kernel alone
     rc = lzf_launch_persistent(f, K, st);
     if (rc != LZ_OK) return rc;
@@ -1237,6 +1316,6 @@ extern "C" int lz_frame_render(const lz_frame_fused* f, lz_timing* timing, lz_st
         else hipLaunchKernelGGL(lz_k_frame_cap_hist<true>, dim3(hb), dim3(1024), lds, st, K);
     }
     LZ_CHECK_LAUNCH("frame_render");
-    if (ref_cap && !f->defer_finish) return lz_frame_finish(f, stream);
+    if (ref_cap && !f->defer_finish) return lzf_finish(f, st, c1sh.p);
     return LZ_OK;
 }

@@ -31,12 +31,14 @@
 #include "lzzx_detmath.h"
 
 // The small per-workgroup table in LDS, LZ_LVTAB_WORDS 32-bit words:
-//   [0,13) level offsets | [16,28) scale (f32) | [32,44) dense row stride res + 1 (0 on hashed levels) | [48] slice queue head of the
+//   [0,13) level offsets | [16,28) scale (f32) | [32,44) dense row stride res + 1 (0 on hashed levels) | f32 heads: [44,48) ind_code
+//   (f32, 0 without one) | [48] slice queue head of the
 //   stand-alone kernels | [49,61) hash multiplier P mod 2^24 (0 on dense levels) | [64,96) enc_a (f32) | [96,108) index mask (size - 1 on
 //   hashed levels, ~0 on dense ones) | f16 heads: [108,124) enc_a as 32 packed halves | [124,126) ind_code as 4 packed halves
 #define LZ_LVTAB_WORDS 128
 #define LZ_LVTAB_SCALE 16
 #define LZ_LVTAB_STRIDE 32
+#define LZ_LVTAB_IND 44
 #define LZ_LVTAB_QUEUE 48
 #define LZ_LVTAB_HMUL 49
 #define LZ_LVTAB_ENCA 64

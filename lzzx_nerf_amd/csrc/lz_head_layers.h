@@ -49,13 +49,16 @@ struct LzHeadArgs {
     int testing;
 };
 
-template <int LAYER, int T>
-__device__ __forceinline__ void lz_layer(const float* __restrict__ wl, int lane, const float (&b)[T][LZ_KS[LAYER]],
-                                         lz_f4 (&acc)[LZ_NT[LAYER]][T]) {
-    constexpr int KS = LZ_KS[LAYER], NT = LZ_NT[LAYER];
+// k-steps K0 .. K1 - 1 of a layer onto the accumulators (an f32 MFMA is a k-ordered fma chain, so a chain split at any k-step and
+// resumed from the accumulators it left is the same chain, bit for bit); wl: the packed fragments, in LDS or in global memory
+template <int LAYER, int T, int K0, int K1>
+__device__ __forceinline__ void lz_layer_ks(const float* __restrict__ wl, int lane, const float (&b)[T][LZ_KS[LAYER]],
+                                            lz_f4 (&acc)[LZ_NT[LAYER]][T]) {
+    constexpr int NT = LZ_NT[LAYER];
+    static_assert(0 <= K0 && K0 <= K1 && K1 <= LZ_KS[LAYER], "k-step range");
     const float* frag = wl + lz_frag_base(LAYER) * 64 + lane;
 #pragma unroll
-    for (int ks = 0; ks < KS; ks++) {
+    for (int ks = K0; ks < K1; ks++) {
         float a[NT];
 #pragma unroll
         for (int ft = 0; ft < NT; ft++) a[ft] = frag[(ks * NT + ft) * 64];
@@ -64,6 +67,11 @@ __device__ __forceinline__ void lz_layer(const float* __restrict__ wl, int lane,
 #pragma unroll
             for (int j = 0; j < T; j++) acc[ft][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ft], b[j][ks], acc[ft][j], 0, 0, 0);
     }
+}
+template <int LAYER, int T>
+__device__ __forceinline__ void lz_layer(const float* __restrict__ wl, int lane, const float (&b)[T][LZ_KS[LAYER]],
+                                         lz_f4 (&acc)[LZ_NT[LAYER]][T]) {
+    lz_layer_ks<LAYER, T, 0, LZ_KS[LAYER]>(wl, lane, b, acc);
 }
 
 __device__ __forceinline__ float lz_relu(float v) { return v > 0.0f ? v : 0.0f; }

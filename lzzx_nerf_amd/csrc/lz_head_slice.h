@@ -19,7 +19,8 @@ struct LzHeadCtx {
     const float* lenca;     // LDS: enc_a [32]
     const float* emb[3];    // the three planes' tables (global)
     float bound, two_bound, eye_v, indq;
-    bool has_eye;
+    const float* lind;      // LDS: ind_code [4] (0 without one)
+    bool has_eye, has_ind;
 };
 
 struct LzHeadOut {
@@ -54,6 +55,9 @@ __device__ __forceinline__ void lz_head_stage(const LzHeadArgs& P, float* wl, ui
     hc.has_eye = P.eye != nullptr;
     hc.eye_v = hc.has_eye ? P.eye[0] : 0.0f;
     hc.indq = P.ind_code ? P.ind_code[q] : 0.0f;
+    hc.has_ind = P.ind_code != nullptr;
+    if (threadIdx.x < 4) wl[L::TAB + LZ_LVTAB_IND + threadIdx.x] = P.ind_code ? P.ind_code[threadIdx.x] : 0.0f;
+    hc.lind = wl + L::TAB + LZ_LVTAB_IND;
 }
 
 // SH(4) source that evaluates the polynomials from a direction fetched on demand (the stand-alone kernels: dirs are per sample)
@@ -61,7 +65,9 @@ template <typename DirFn>
 struct LzShFromDir {
     DirFn dirfn;
     float o[16];
+    static constexpr bool C1_PARTIAL = false;    // the slice runs all of colour_net.0
     __device__ __forceinline__ explicit LzShFromDir(DirFn f) : dirfn(f) {}
+    __device__ __forceinline__ void issue(int) {}
     __device__ __forceinline__ void prepare() {
         float dx, dy, dz;
         dirfn(dx, dy, dz);
@@ -77,8 +83,40 @@ struct LzShFromDir {
 template <typename DirFn>
 __device__ __forceinline__ LzShFromDir<DirFn> lz_sh_from_dir(DirFn f) { return LzShFromDir<DirFn>(f); }
 
+// Per-ray SH partial of colour_net.0.  The layer's input is [SH 16 | geo 64 | ind 4] and its accumulators start at zero, so after k-step 3
+// (the 16 SH components) they hold an fma chain over the view direction and the weights alone: the same bits for every sample of a ray.
+// lz_c1_sh_partial runs those 4 k-steps x 4 tiles once for 16 rays (lane (s, q): ray s); the fused frame stores the result per ray, 64 f32
+// in the lane order the slice consumes -- lane (s, q) owns features 16 ft + 4 q + r at floats 16 q + 4 ft + r of its ray's row, 4 x 16 B --
+// and its slices resume the chain at k-step 4 (LzShPartial).  Same instruction, same operands, same order: nothing moves by a bit.
+constexpr int LZ_C1_SH_KS = 4;             // k-steps of colour_net.0 that consume SH only
+constexpr int LZ_C1_SH_FLOATS = 64;        // per ray
+template <typename ShFn>
+__device__ __forceinline__ void lz_c1_sh_partial(const float* __restrict__ wl, int lane, ShFn& sh, lz_f4 (&acc)[4][1]) {
+    const int q = lane >> 4;
+    float b[1][LZ_KS[LZ_L_C1]];
+    sh.prepare();
+#pragma unroll
+    for (int i = 0; i < LZ_KS[LZ_L_C1]; i++) b[0][i] = i < LZ_C1_SH_KS ? sh.comp_iq(i, q) : 0.0f;
+#pragma unroll
+    for (int ft = 0; ft < 4; ft++) acc[ft][0] = lz_f4{0, 0, 0, 0};
+    lz_layer_ks<LZ_L_C1, 1, 0, LZ_C1_SH_KS>(wl, lane, b, acc);
+}
+// the slice's SH source when the partial exists: `row` = this lane's 16 floats of its ray's partial (null: no ray in the slot -- the
+// sample's outputs are discarded).  issue() starts the 4 loads well ahead of colour_net.0 (the other waves' MFMAs cover them).
+struct LzShPartial {
+    static constexpr bool C1_PARTIAL = true;
+    const float* row;
+    lz_f4 p[4];
+    __device__ __forceinline__ void issue(int) {
+#pragma unroll
+        for (int ft = 0; ft < 4; ft++) p[ft] = row ? *reinterpret_cast<const lz_f4*>(row + 4 * ft) : lz_f4{0, 0, 0, 0};
+    }
+    __device__ __forceinline__ lz_f4 part(int ft) const { return p[ft]; }
+};
+
 // one slice: (px, py, pz) = this lane's sample position; shfn supplies SH(4) of its view direction when the colour net needs it
-// (LzShFromDir: evaluated here from the direction, like the reference per sample; the fused frame kernel reads it per ray from LDS)
+// (LzShFromDir: evaluated here from the direction, like the reference per sample), or the colour net's SH partial of the sample's ray
+// (LzShPartial: the fused frame kernel, which evaluates k-steps 0 .. 3 of colour_net.0 once per ray)
 // FOLD (inference only): geo = Wg s2 feeds colour_net.0 with nothing but a linear map in between (network.py:304-306), so
 // W_c0[:, geo] (Wg s2) = (W_c0[:, geo] Wg) s2: the host packs the 64 x 64 product into colour_net.0's geo columns (head.py: fold_geo) and
 // the slice hands s2 to the colour net directly -- 64 of the 361 MFMAs per slice are never issued.  sigma (the VALU row of sigma_net.2 on
@@ -185,14 +223,32 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
             for (int t = 0; t < 2; t++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) b1[j][9 + 4 * t + r] = hc.lenca[16 * t + 4 * q + r] * att[j][4 * t + r];
-            b1[j][17] = (hc.has_eye && q == 0) ? hc.eye_v * eyeatt[j] : 0.0f;
+            b1[j][17] = 0.0f;           // (k-step 17 runs on the VALU below)
         }
         lz_f4 acc1[4][LZ_T];
 #pragma unroll
         for (int ft = 0; ft < 4; ft++)
 #pragma unroll
             for (int j = 0; j < LZ_T; j++) acc1[ft][j] = lz_f4{0, 0, 0, 0};
-        lz_layer<LZ_L_S1, LZ_T>(hc.wl, lane, b1, acc1);
+        lz_layer_ks<LZ_L_S1, LZ_T, 0, 17>(hc.wl, lane, b1, acc1);
+        // k-step 17 = [eye * eye_att | 0 0 0] (input 68, then padding) and the last link of the chain: its MFMA adds W[n, 68] e on top of
+        // k-step 16, then three products 0 * 0, which can flip nothing but the sign of a zero accumulator -- and the ReLU behind maps both
+        // zeros to +0.  So it is one fma per output feature on the VALU: every lane of a sample holds the same eyeatt bits (lz_lane_dot),
+        // and lane (s, q) needs W[16 ft + 4 q + r, 68] = entries 4 q .. 4 q + 3 of the A fragment (17, ft): one 16-byte LDS read per tile,
+        // 16 fmas instead of 4 MFMAs.  Without the eye input the k-step adds zeros only: skipped.
+        if (hc.has_eye) {
+            const float* w68 = hc.wl + (lz_frag_base(LZ_L_S1) + 17 * LZ_NT[LZ_L_S1]) * 64 + 4 * q;
+#pragma unroll
+            for (int j = 0; j < LZ_T; j++) {
+                const float e = hc.eye_v * eyeatt[j];
+#pragma unroll
+                for (int ft = 0; ft < 4; ft++) {
+                    const lz_f4 w = *reinterpret_cast<const lz_f4*>(w68 + 64 * ft);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) acc1[ft][j][r] = lz_fmaf(w[r], e, acc1[ft][j][r]);
+                }
+            }
+        }
         float b2[LZ_T][16];
 #pragma unroll
         for (int j = 0; j < LZ_T; j++)
@@ -200,6 +256,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
             for (int ft = 0; ft < 4; ft++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_relu(acc1[ft][j][r]);
+        shfn.issue(q);            // the per-ray SH partial of colour_net.0 (LzShPartial): its loads fly under sigma_net.1 / .2
         lz_f4 acc2[4][LZ_T];
 #pragma unroll
         for (int ft = 0; ft < 4; ft++)
@@ -238,24 +295,51 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
     // ---------------- colour net: [SH 16 | geo 64 | ind 4] -> 64 -> 3 ----------------
     float rgb[LZ_T][3];
     {
+        // k-step 20 (ind_code) runs on the VALU (below), except with FOLD: there it spills the folded frame kernels, and stays an MFMA
+        constexpr bool IND_VALU = !FOLD;
         float b1[LZ_T][21];
-#pragma unroll
-        for (int j = 0; j < LZ_T; j++) {
-            // SH(4) of the view direction (constant per ray, recomputed per sample like the reference): this lane
-            // keeps components 4i + q
-            shfn.prepare();
-#pragma unroll
-            for (int i = 0; i < 4; i++) b1[j][i] = shfn.comp_iq(i, q);     // SH component 4 i + q
-#pragma unroll
-            for (int k = 0; k < 16; k++) b1[j][4 + k] = geo[j][k];
-            b1[j][20] = hc.indq;
-        }
         lz_f4 acc1[4][LZ_T];
 #pragma unroll
-        for (int ft = 0; ft < 4; ft++)
+        for (int j = 0; j < LZ_T; j++) {
+            if constexpr (ShFn::C1_PARTIAL) {
+                // k-steps 0 .. 3 done per ray (lz_c1_sh_partial): the chain resumes from their accumulators
 #pragma unroll
-            for (int j = 0; j < LZ_T; j++) acc1[ft][j] = lz_f4{0, 0, 0, 0};
-        lz_layer<LZ_L_C1, LZ_T>(hc.wl, lane, b1, acc1);
+                for (int i = 0; i < LZ_C1_SH_KS; i++) b1[j][i] = 0.0f;
+#pragma unroll
+                for (int ft = 0; ft < 4; ft++) acc1[ft][j] = shfn.part(ft);
+            } else {
+                // SH(4) of the view direction (constant per ray, recomputed per sample like the reference): this lane
+                // keeps components 4i + q
+                shfn.prepare();
+#pragma unroll
+                for (int i = 0; i < 4; i++) b1[j][i] = shfn.comp_iq(i, q);     // SH component 4 i + q
+#pragma unroll
+                for (int ft = 0; ft < 4; ft++) acc1[ft][j] = lz_f4{0, 0, 0, 0};
+            }
+#pragma unroll
+            for (int k = 0; k < 16; k++) b1[j][4 + k] = geo[j][k];
+            b1[j][20] = IND_VALU ? 0.0f : hc.indq;     // (k-step 20, ind_code, runs on the VALU below unless FOLD)
+        }
+        lz_layer_ks<LZ_L_C1, LZ_T, ShFn::C1_PARTIAL ? LZ_C1_SH_KS : 0, LZ_KS[LZ_L_C1] - (IND_VALU ? 1 : 0)>(hc.wl, lane, b1, acc1);
+        // k-step 20 = the 4 ind_code inputs, the same for every sample and the last link of the chain: on the VALU, acc = fma(W[n, 80 + k],
+        // ind[k], acc) for k = 0 .. 3 in the MFMA's order (an f32 MFMA is a k-ordered fma chain).  Lane (s, q) needs W[16 ft + 4 q + r, 80 + k]
+        // = entries 16 k + 4 q .. 16 k + 4 q + 3 of the A fragment (20, ft): 16 ds_read_b128 and 64 fmas instead of 4 MFMAs (measured: the
+        // f32 frame 1.1 % faster; the same move for a per-sample k-step, whose B values first cross lanes, was 3-6 % SLOWER).  Without
+        // ind_code the k-step adds zeros only: skipped.
+        if (IND_VALU && hc.has_ind) {
+            const float* w80 = hc.wl + (lz_frag_base(LZ_L_C1) + 20 * LZ_NT[LZ_L_C1]) * 64 + 4 * q;
+            const lz_f4 ind = *reinterpret_cast<const lz_f4*>(hc.lind);      // (one broadcast read)
+#pragma unroll
+            for (int j = 0; j < LZ_T; j++)
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+#pragma unroll
+                    for (int ft = 0; ft < 4; ft++) {
+                        const lz_f4 w = *reinterpret_cast<const lz_f4*>(w80 + 64 * ft + 16 * k);
+#pragma unroll
+                        for (int r = 0; r < 4; r++) acc1[ft][j][r] = lz_fmaf(w[r], ind[k], acc1[ft][j][r]);
+                    }
+        }
         float b2[LZ_T][16];
 #pragma unroll
         for (int j = 0; j < LZ_T; j++)
