@@ -1,5 +1,5 @@
-// lz_head_bwd_common.h -- pieces shared by the two backward kernels of the fused head (lz_head_bwd.hip: activations recomputed;
-// lz_head_rec.hip: activations recorded by the forward): the transposed-fragment layer, record stores, ReLU masks.
+// lz_head_bwd_common.h -- pieces of the backward kernels of the fused head (lz_head_rec.hip: activations recorded by the forward or
+// recomputed; lz_head_gradw.hip: the weight-gradient pass): the transposed-fragment layer, record stores, ReLU masks.
 #ifndef LZ_HEAD_BWD_COMMON_H
 #define LZ_HEAD_BWD_COMMON_H
 #include "lz_head_layers.h"
@@ -33,8 +33,9 @@ struct LzHeadBwdArgs {
     const float *g_sigma, *g_rgb, *g_amb_aud, *g_amb_eye, *g_unc;     // upstream gradients [M], [M,3], [M], [M], [M]
     lz_head_bwd_out o;
     const void* wb16;   // transposed f16 fragments (lz_head_pack_weights_bwd_f16) for the backward on the f16 matrix cores, else null
-    // the recomputing arrangement (lz_k_triplane_head_backward_rec<.., RC>): the forward's f16 weight image (lz_head_pack_weights_f16), unc_net's
-    // five fragments (lz_head_pack_unc_f16) and the samples' view directions; the kernel's `st` argument is then the forward's encx16
+    // the recomputing arrangements (lz_k_triplane_head_backward_rec<1, 1, 1, 1>): the forward's f16 weight image (lz_head_pack_weights_f16),
+    // unc_net's five fragments (lz_head_pack_unc_f16) and the samples' view directions; the kernel's `st` argument is then the forward's encx16
+    // (<0, 0, 0, 1>: only the view directions; `st` = the positions)
     const void* fw16 = nullptr;
     const void* unc16 = nullptr;
     const float* dirs = nullptr;

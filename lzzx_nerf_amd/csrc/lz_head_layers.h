@@ -1,5 +1,5 @@
 // lz_head_layers.h -- layer tables, packed-weight layout and the per-layer MFMA / VALU helpers shared by the forward
-// (lz_head.hip) and backward (lz_head_bwd.hip) fused-head kernels.
+// (lz_head.hip, lz_head_rec.hip) and backward (lz_head_rec.hip) fused-head kernels.
 #ifndef LZ_HEAD_LAYERS_H
 #define LZ_HEAD_LAYERS_H
 #include "lz_common.h"

@@ -1,11 +1,11 @@
-// lz_head_rec.hip -- the fused triplane head for TRAINING without the recompute: a forward that records what the backward needs,
-// and a backward that starts from that record (NeRFNetwork.forward, nerf_triplane/network.py:252-311, training mode).
+// lz_head_rec.hip -- the fused triplane head for TRAINING: a forward that records what the backward needs, and a backward that starts
+// from that record or recomputes it (NeRFNetwork.forward, nerf_triplane/network.py:252-311, training mode).
 //
-// lz_head_bwd.hip recomputes the forward inside the backward kernel: 379 of its 759 MFMAs per 16-sample slice, on a kernel that is
-// bound by the matrix pipe.  Here the forward kernel (the same instruction sequence as lz_k_triplane_head<true>, so the five outputs
-// have the same bits) also writes
+// The recomputing backward (XYZ below) runs the forward again: 379 of its 759 MFMAs per 16-sample slice, on a kernel that
+// is bound by the matrix pipe.  Here the forward kernel (lz_fwd32_chain: the same instruction sequence as lz_k_triplane_head<true>, so the
+// five outputs have the same bits) also writes
 //   * the X half of the per-sample record (the wide layers' inputs, which the weight-gradient pass reads: the recomputing backward
-//     wrote exactly these columns itself), and
+//     writes exactly these columns itself), and
 //   * a state row per sample (LZ_FWD_STATE floats): att, the inputs of the three skinny output layers, the ReLU masks as bits and
 //     seven scalars (||att||, eye_att, the pre-activations of unc / sigma / rgb),
 // and the backward kernel reads the state row instead of xyz / dirs / the tables: no gather, no SH, no forward matrix work.  The
@@ -14,6 +14,7 @@
 
 #include "lz_head_bwd_common.h"
 #include "lz_head_fwd16_chain.h"   // RC: the f16 forward chain, recomputed in the backward
+#include "lz_head_fwd32_chain.h"   // the f32 forward chain: the recording forward, and recomputed in the backward (XYZ)
 #include "lz_head_gather.h"
 #include "lz_head_slice.h"
 #include "lzzx_sh_eval.h"
@@ -59,6 +60,80 @@ __device__ __forceinline__ void lz_unpack_pair(const lz_v4& w, float* lo4, float
 // ------------------------------------------------------------------------------------------------
 // forward, recording
 // ------------------------------------------------------------------------------------------------
+// the sink of lz_fwd32_chain that stores the X half of this sample's record (rb) and its state row (sb) in the f32 or f16 layout
+template <bool H16>
+struct LzRecSink {
+    float* rb;
+    float* sb;
+    int q;
+    __device__ __forceinline__ void x_a1(const float (&a1)[16]) {
+        if constexpr (H16) {
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_A1 / 2, a1, 0);
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_A1 / 2 + 1, a1, 2);
+        } else {
+            lz_dump_chained<4>(rb, q, LZ_BWD_X_A1, a1);
+        }
+    }
+    __device__ __forceinline__ void st_att(const float (&att)[8]) { lz_dump_chained<2>(sb, q, LZ_ST_ATT, att); }   // f32 in both layouts: the data gradient uses it
+    __device__ __forceinline__ void st_e1(const float (&e1)[4]) {
+        if constexpr (H16) lz_dump_pair(sb + 4 * q, LZ_S16_E1 / 16, e1[0], e1[1], e1[2], e1[3], 0.0f, 0.0f, 0.0f, 0.0f);
+        else lz_dump_chained<1>(sb, q, LZ_ST_E1, e1);
+    }
+    __device__ __forceinline__ void st_u1(const float (&u1)[8]) {
+        if constexpr (H16) lz_dump_pair_chained(sb + 4 * q, LZ_S16_U1 / 16, u1, 0);
+        else lz_dump_chained<2>(sb, q, LZ_ST_U1, u1);
+    }
+    __device__ __forceinline__ void x_sig0(const float (&encx)[9], const float (&encw)[8], float eterm) {
+        if constexpr (H16) {
+            // tiles 0, 1: enc_x features 4 i + q, i < 8 (half 2 r + p of the lane's eight = i); tile 2: feature 32 + q at column
+            // 4 q, the eye term at column 1; tiles 3, 4: enc_a * att; tile 5: padding
+            lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2, encx[0], encx[2], encx[4], encx[6], encx[1], encx[3], encx[5], encx[7]);
+            lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2 + 1, encx[8], eterm, 0.0f, 0.0f, encw[0], encw[1], encw[2], encw[3]);
+            lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2 + 2, encw[4], encw[5], encw[6], encw[7], 0.0f, 0.0f, 0.0f, 0.0f);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 9; i++) rb[lz_tcol(LZ_BWD_X_SIG0 + 4 * i + q)] = encx[i];
+            lz_dump_chained<2>(rb, q, LZ_BWD_X_SIG0 + 36, encw);
+            rb[lz_tcol(LZ_BWD_X_SIG0 + 68 + q)] = eterm;   // lanes q > 0 write zeros into the padding columns 69..71
+        }
+    }
+    __device__ __forceinline__ void x_s1(const float (&s1)[16]) {
+        if constexpr (H16) {
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S1 / 2, s1, 0);
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S1 / 2 + 1, s1, 2);
+        } else {
+            lz_dump_chained<4>(rb, q, LZ_BWD_X_S1, s1);
+        }
+    }
+    __device__ __forceinline__ void x_s2(const float (&s2)[16]) {
+        if constexpr (H16) {
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S2C / 2, s2, 0);
+            lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S2C / 2 + 1, s2, 2);
+        } else {
+            lz_dump_chained<4>(rb, q, LZ_BWD_X_S2C, s2);
+        }
+    }
+    __device__ __forceinline__ void x_c1(float sh0, float sh1, float sh2, float sh3, float indq) {
+        if constexpr (H16) {   // tile 4: SH component 4 r + q at column 4 q + r; tile 5: ind_code[q] at column 4 q
+            lz_dump_pair(rb + 4 * q, LZ_R16_X_S2C / 2 + 2, sh0, sh1, sh2, sh3, indq, 0.0f, 0.0f, 0.0f);
+        } else {
+            rb[lz_tcol(LZ_BWD_X_S2C + 64 + q)] = sh0;
+            rb[lz_tcol(LZ_BWD_X_S2C + 68 + q)] = sh1;
+            rb[lz_tcol(LZ_BWD_X_S2C + 72 + q)] = sh2;
+            rb[lz_tcol(LZ_BWD_X_S2C + 76 + q)] = sh3;
+            rb[lz_tcol(LZ_BWD_X_S2C + 80 + q)] = indq;
+        }
+    }
+    __device__ __forceinline__ void st_c1(const float (&c1)[16]) {
+        if constexpr (H16) {
+            lz_dump_pair_chained(sb + 4 * q, LZ_S16_C1 / 16, c1, 0);
+            lz_dump_pair_chained(sb + 4 * q, LZ_S16_C1 / 16 + 1, c1, 2);
+        } else {
+            lz_dump_chained<4>(sb, q, LZ_ST_C1, c1);
+        }
+    }
+};
+
 template <bool H16>
 __global__ void __launch_bounds__(LZ_FREC_WG, 1)
 lz_k_triplane_head_forward_rec(LzHeadArgs P, const float* __restrict__ xyzs, const float* __restrict__ dirs, uint32_t M,
@@ -74,9 +149,8 @@ lz_k_triplane_head_forward_rec(LzHeadArgs P, const float* __restrict__ xyzs, con
     LzHeadCtx hc;
     lz_head_stage<true>(P, wl, LZ_FREC_WG, q, hc);
     __syncthreads();
-    const float* wv = wl + LzHeadLds<true>::WV;
     int* queue = reinterpret_cast<int*>(wl + LzHeadLds<true>::TAB) + LZ_LVTAB_QUEUE;
-    for (int w = threadIdx.x >> 8; w > 0; w--) {   // see lz_k_triplane_head_backward: the waves that share a SIMD start a part of a slice apart
+    for (int w = threadIdx.x >> 8; w > 0; w--) {   // see lz_k_triplane_head_backward_rec: the waves that share a SIMD start a part of a slice apart
         __builtin_amdgcn_s_sleep(127);
         __builtin_amdgcn_s_sleep(127);
     }
@@ -103,7 +177,6 @@ lz_k_triplane_head_forward_rec(LzHeadArgs P, const float* __restrict__ xyzs, con
         const uint32_t base = (slice_lo + (uint32_t)slice) * 16;
         const bool valid = base + s < M;
         const uint32_t m = valid ? base + s : M - 1;   // clamped lanes repeat the last row: the same values are stored again
-        const size_t row = m;
         float* rb = lz_blk(rec, slice_lo + (uint32_t)slice, H16 ? LZ_BWD_REC16 / 2 : LZ_BWD_REC, s);   // f16: rows counted in dwords
         float* sb = lz_blk(st, slice_lo + (uint32_t)slice, H16 ? LZ_FWD_STATE16 : LZ_FWD_STATE, s);
 
@@ -117,203 +190,23 @@ lz_k_triplane_head_forward_rec(LzHeadArgs P, const float* __restrict__ xyzs, con
             dir0 = dirs[r1 * 3]; dir1 = dirs[r1 * 3 + 1]; dir2 = dirs[r1 * 3 + 2];
         }
         __builtin_amdgcn_sched_barrier(0);
-        const float bx[1][9] = {{encx[0], encx[1], encx[2], encx[3], encx[4], encx[5], encx[6], encx[7], encx[8]}};
-        // audio channel attention
-        float att[8];
-        uint32_t mk_a1;
-        {
-            lz_f4 acc1[4][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_A1, 1>(wl, lane, bx, acc1);
-            float a1[1][16];
-#pragma unroll
-            for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) a1[0][4 * ft + r] = lz_relu(acc1[ft][0][r]);
-            mk_a1 = lz_mask_pos(a1[0]);
-            {
-                if constexpr (H16) {
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_A1 / 2, a1[0], 0);
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_A1 / 2 + 1, a1[0], 2);
-                } else {
-                    lz_dump_chained<4>(rb, q, LZ_BWD_X_A1, a1[0]);
-                }
-            }
-            lz_f4 acc2[2][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_A2, 1>(wl, lane, a1, acc2);
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) att[4 * ft + r] = acc2[ft][0][r];
-        }
-        lz_dump_chained<2>(sb, q, LZ_ST_ATT, att);   // f32 in both layouts: the data gradient uses it
-        float norm;
-        {
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 8; k++) acc = lz_fmaf(att[k], att[k], acc);
-            acc += __shfl_xor(acc, 16, 64);
-            acc += __shfl_xor(acc, 32, 64);
-            norm = sqrtf(acc);
-        }
-        // eye attention
-        float eyeatt = 0.0f;
-        uint32_t mk_e1 = 0;
-        if (hc.has_eye) {
-            lz_f4 acce[1][1] = {{lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_E1, 1>(wl, lane, bx, acce);
-            float e1[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) e1[r] = lz_relu(acce[0][0][r]);
-            mk_e1 = lz_mask_pos(e1);
-            {
-                if constexpr (H16) lz_dump_pair(sb + 4 * q, LZ_S16_E1 / 16, e1[0], e1[1], e1[2], e1[3], 0.0f, 0.0f, 0.0f, 0.0f);
-                else lz_dump_chained<1>(sb, q, LZ_ST_E1, e1);
-            }
-            eyeatt = lz_sigmoidf(lz_lane_dot<1>(wv + LZ_WV_E2, q, e1));
-        }
-        // uncertainty
-        float upre;
-        uint32_t mk_u1;
-        {
-            lz_f4 accu[2][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_U1, 1>(wl, lane, bx, accu);
-            float u1[8];
-#pragma unroll
-            for (int ft = 0; ft < 2; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) u1[4 * ft + r] = lz_relu(accu[ft][0][r]);
-            mk_u1 = lz_mask_pos(u1);
-            {
-                if constexpr (H16) lz_dump_pair_chained(sb + 4 * q, LZ_S16_U1 / 16, u1, 0);
-                else lz_dump_chained<2>(sb, q, LZ_ST_U1, u1);
-            }
-            upre = lz_lane_dot<2>(wv + LZ_WV_U2, q, u1);
-        }
-        // sigma net
-        float spre;
-        uint32_t mk_s1, mk_s2;
-        float geo[1][16];
-        {
-            float b1[1][18];
-#pragma unroll
-            for (int i = 0; i < 9; i++) b1[0][i] = encx[i];
-            float encw[8];
-#pragma unroll
-            for (int t = 0; t < 2; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) encw[4 * t + r] = hc.lenca[16 * t + 4 * q + r] * att[4 * t + r];
-#pragma unroll
-            for (int k = 0; k < 8; k++) b1[0][9 + k] = encw[k];
-            b1[0][17] = (hc.has_eye && q == 0) ? hc.eye_v * eyeatt : 0.0f;
-            {   // sigma_net.0 input [enc_x 36 | enc_a * att 32 | eye * eye_att 1]
-                if constexpr (H16) {
-                    // tiles 0, 1: enc_x features 4 i + q, i < 8 (half 2 r + p of the lane's eight = i); tile 2: feature 32 + q at column
-                    // 4 q, the eye term at column 1; tiles 3, 4: enc_a * att; tile 5: padding
-                    lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2, encx[0], encx[2], encx[4], encx[6], encx[1], encx[3], encx[5], encx[7]);
-                    lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2 + 1, encx[8], b1[0][17], 0.0f, 0.0f, encw[0], encw[1], encw[2], encw[3]);
-                    lz_dump_pair(rb + 4 * q, LZ_R16_X_SIG0 / 2 + 2, encw[4], encw[5], encw[6], encw[7], 0.0f, 0.0f, 0.0f, 0.0f);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 9; i++) rb[lz_tcol(LZ_BWD_X_SIG0 + 4 * i + q)] = encx[i];
-                    lz_dump_chained<2>(rb, q, LZ_BWD_X_SIG0 + 36, encw);
-                    rb[lz_tcol(LZ_BWD_X_SIG0 + 68 + q)] = b1[0][17];   // lanes q > 0 write zeros into the padding columns 69..71
-                }
-            }
-            lz_f4 acc1[4][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_S1, 1>(wl, lane, b1, acc1);
-            float s1[1][16];
-#pragma unroll
-            for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) s1[0][4 * ft + r] = lz_relu(acc1[ft][0][r]);
-            mk_s1 = lz_mask_pos(s1[0]);
-            {
-                if constexpr (H16) {
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S1 / 2, s1[0], 0);
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S1 / 2 + 1, s1[0], 2);
-                } else {
-                    lz_dump_chained<4>(rb, q, LZ_BWD_X_S1, s1[0]);
-                }
-            }
-            lz_f4 acc2[4][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_S2, 1>(wl, lane, s1, acc2);
-            float s2[1][16];
-#pragma unroll
-            for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) s2[0][4 * ft + r] = lz_relu(acc2[ft][0][r]);
-            mk_s2 = lz_mask_pos(s2[0]);
-            {
-                if constexpr (H16) {
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S2C / 2, s2[0], 0);
-                    lz_dump_pair_chained(rb + 4 * q, LZ_R16_X_S2C / 2 + 1, s2[0], 2);
-                } else {
-                    lz_dump_chained<4>(rb, q, LZ_BWD_X_S2C, s2[0]);
-                }
-            }
-            lz_f4 acc3[4][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_S3, 1>(wl, lane, s2, acc3);
-#pragma unroll
-            for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) geo[0][4 * ft + r] = acc3[ft][0][r];
-            spre = lz_lane_dot<4>(wv + LZ_WV_SIG, q, s2[0]);
-        }
-        // colour net
-        float cpre[3];
-        uint32_t mk_c1;
-        {
-            float o[16];
-            lz_sh_eval(cd0, cd1, cd2, 4, o, nullptr, nullptr, nullptr);
-            float b1[1][21];
-#pragma unroll
-            for (int i = 0; i < 4; i++) b1[0][i] = q == 0 ? o[4 * i] : (q == 1 ? o[4 * i + 1] : (q == 2 ? o[4 * i + 2] : o[4 * i + 3]));
-#pragma unroll
-            for (int k = 0; k < 16; k++) b1[0][4 + k] = geo[0][k];
-            b1[0][20] = hc.indq;
-            {   // colour_net.0 input [SH 16 | geo 64 | ind 4]; geo = s2 . Wg^T is not stored (lz_head_bwd.hip)
-                if constexpr (H16) {   // tile 4: SH component 4 r + q at column 4 q + r; tile 5: ind_code[q] at column 4 q
-                    lz_dump_pair(rb + 4 * q, LZ_R16_X_S2C / 2 + 2, b1[0][0], b1[0][1], b1[0][2], b1[0][3], hc.indq, 0.0f, 0.0f, 0.0f);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; i++) rb[lz_tcol(LZ_BWD_X_S2C + 64 + 4 * i + q)] = b1[0][i];
-                    rb[lz_tcol(LZ_BWD_X_S2C + 80 + q)] = hc.indq;
-                }
-            }
-            lz_f4 acc1[4][1] = {{lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}, {lz_f4{0, 0, 0, 0}}};
-            lz_layer<LZ_L_C1, 1>(wl, lane, b1, acc1);
-            float c1[16];
-#pragma unroll
-            for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) c1[4 * ft + r] = lz_relu(acc1[ft][0][r]);
-            mk_c1 = lz_mask_pos(c1);
-            {
-                if constexpr (H16) {
-                    lz_dump_pair_chained(sb + 4 * q, LZ_S16_C1 / 16, c1, 0);
-                    lz_dump_pair_chained(sb + 4 * q, LZ_S16_C1 / 16 + 1, c1, 2);
-                } else {
-                    lz_dump_chained<4>(sb, q, LZ_ST_C1, c1);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < 3; c++) cpre[c] = lz_lane_dot<4>(wv + LZ_WV_C2 + 64 * c, q, c1);
-        }
-        const float sigma = lz_expf(spre);
+        LzRecSink<H16> sink{rb, sb, q};
+        LzFwd32Out fo;
+        lz_fwd32_chain(hc, lane, encx, cd0, cd1, cd2, sink, fo);
         {
             // masks + one scalar per lane: q = 0 ||att||, 1 eye_att, 2 unc pre-activation, 3 sigma
-            const float sc = q == 0 ? norm : (q == 1 ? eyeatt : (q == 2 ? upre : sigma));
-            lz_v4 w = {__uint_as_float(mk_a1 | (mk_s1 << 16)), __uint_as_float(mk_s2 | (mk_c1 << 16)), __uint_as_float(mk_u1 | (mk_e1 << 8)), sc};
+            const float sc = q == 0 ? fo.norm : (q == 1 ? fo.eyeatt : (q == 2 ? fo.upre : fo.sigma));
+            lz_v4 w = {__uint_as_float(fo.mk_a1 | (fo.mk_s1 << 16)), __uint_as_float(fo.mk_s2 | (fo.mk_c1 << 16)), __uint_as_float(fo.mk_u1 | (fo.mk_e1 << 8)), sc};
             LZ_REC_STORE(w, reinterpret_cast<lz_v4*>(sb + lz_tcol((H16 ? LZ_S16_MK : LZ_ST_MK) + 4 * q)));
             // the four lanes of a sample hold the same bits: all of them store (same address, same value), no lane-dependent branch
-            lz_v4 cw = {cpre[0], cpre[1], cpre[2], 0.0f};
+            lz_v4 cw = {fo.cpre[0], fo.cpre[1], fo.cpre[2], 0.0f};
             LZ_REC_STORE(cw, reinterpret_cast<lz_v4*>(sb + lz_tcol(H16 ? LZ_S16_CLR : LZ_ST_CLR)));
-            sigmas[m] = sigma;
-            amb_aud[m] = norm;
-            if (amb_eye) amb_eye[m] = eyeatt;
-            unc_out[m] = lz_softplusf(upre);
+            sigmas[m] = fo.sigma;
+            amb_aud[m] = fo.norm;
+            if (amb_eye) amb_eye[m] = fo.eyeatt;
+            unc_out[m] = lz_softplusf(fo.upre);
             const int qc = q < 2 ? q : 2;
-            const float cv = q == 0 ? cpre[0] : (q == 1 ? cpre[1] : cpre[2]);
+            const float cv = q == 0 ? fo.cpre[0] : (q == 1 ? fo.cpre[1] : fo.cpre[2]);
             rgbs[(size_t)m * 3 + qc] = lz_sigmoidf(cv) * 1.002f - 0.001f;
         }
         slice = next;
@@ -352,11 +245,18 @@ lz_k_triplane_head_forward_rec(LzHeadArgs P, const float* __restrict__ xyzs, con
 // FUSE does.  The f16 forward fragments (59 + 5 KB) take the place of the second G / X buffer in LDS, so every segment pays the second
 // barrier of the single-buffer arrangement.  Per sample and step: 80 B written by the forward and 80 + 40 B read here, instead of
 // 1 216 B of record + state written and read.
-template <bool H16, bool B16, bool FUSE = false, bool RC = false>
+// XYZ (RECOMPUTE with f32 records, neither B16 nor FUSE: record=False of the f32 head): nothing at all is read back from the forward,
+// `st` = the positions.  The wave gathers enc_x and runs the f32 forward chain of its slice (lz_fwd32_chain, the function the recording
+// forward runs: 379 of the slice's 759 MFMAs) with a sink that writes the X half of the f32 record as that forward does and keeps the state
+// row in registers, then goes on as from a recorded state row.
+// RECOMPUTE: the forward runs again in this kernel instead of being read back; the record precision picks the chain (H16: RC, else XYZ).
+template <bool H16, bool B16, bool FUSE = false, bool RECOMPUTE = false>
 __global__ void __launch_bounds__(LZ_BWD_WG, LZ_BWD_WG / 256)
 lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, uint32_t M, float* __restrict__ parts) {
+    constexpr bool RC = RECOMPUTE && H16, XYZ = RECOMPUTE && !H16;
     static_assert(!FUSE || H16, "the fused weight-gradient products run on half operands (f16 records)");
-    static_assert(!RC || (H16 && B16 && FUSE), "the recomputing arrangement is the all-f16 one with fused weight gradients");
+    static_assert(!RC || (B16 && FUSE), "the f16 recomputing arrangement is the all-f16 one with fused weight gradients");
+    static_assert(!XYZ || (!B16 && !FUSE), "the f32 recomputing arrangement runs the f32 data-gradient chain and writes f32 records");
     constexpr int NFRAG = LZ_FRAGS_ALL;
     constexpr int WV = B16 ? LZ_BFRAGS * 128 : NFRAG * 64, TAB = WV + LZ_WV_FLOATS;
     constexpr uint32_t NBUF = (B16 && !RC) ? 2u : 1u;          // FUSE: LDS buffers of G / X tiles
@@ -364,6 +264,7 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
     constexpr int FW16 = TAB + LZ_LVTAB_WORDS + FUSE_FLOATS;                        // RC: f16 forward fragments, then unc_net's five
     constexpr int FW16_FLOATS = RC ? (H_FRAGS + LZ_UNC16_FRAGS) * 64 * 4 : 0;
     static_assert((FW16 + FW16_FLOATS) * 4 <= 163840, "LDS budget of one workgroup per CU");
+    static_assert(!XYZ || FW16 == LzHeadLds<true>::FLOATS, "XYZ: the weight image and tables where lz_head_stage puts them");
     __shared__ __align__(16) float wl[FW16 + FW16_FLOATS];
     const LzHeadArgs& P = A.fwd;
     const lz_head_bwd_out& O = A.o;
@@ -371,7 +272,10 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
     const uint32_t slice_lo = (uint32_t)(((uint64_t)n_slices * blockIdx.x) / gridDim.x);
     const uint32_t slice_hi = (uint32_t)(((uint64_t)n_slices * (blockIdx.x + 1)) / gridDim.x);
     if (slice_lo >= slice_hi) return;
-    {
+    LzHeadCtx hc;   // XYZ: the forward chain's context (the LDS image of this kernel is lz_head_stage's, with the level table for the gather)
+    if constexpr (XYZ) {
+        lz_head_stage<true>(P, wl, LZ_BWD_WG, (int)(threadIdx.x & 63) >> 4, hc);
+    } else {
         const float4* src = reinterpret_cast<const float4*>(B16 ? A.wb16 : P.packed);
         float4* dst = reinterpret_cast<float4*>(wl);
         for (int i = threadIdx.x; i < WV / 4; i += LZ_BWD_WG) dst[i] = src[i];
@@ -403,14 +307,17 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
     const bool has_eye = P.eye != nullptr;
     const float eye_v = has_eye ? P.eye[0] : 0.0f;
     int* queue = reinterpret_cast<int*>(wl + TAB) + LZ_LVTAB_QUEUE;
+    // The two waves that share a SIMD would otherwise run in lockstep (same code, same start): both in their matrix phases, then both in
+    // their VALU / store phases.  Delaying the second one by about half a slice lets one wave's MFMAs overlap the other's VALU work.
     if ((threadIdx.x >> 6) >= 4) {
         __builtin_amdgcn_s_sleep(127);
         __builtin_amdgcn_s_sleep(127);
+        if constexpr (XYZ) __builtin_amdgcn_s_sleep(127);   // (its slice is the forward longer)
     }
     float acc_enca[8], acc_ind = 0.0f;   // d(enc_a)[16 t + 4 q + r], d(ind_code)[q], summed over this lane's samples
 #pragma unroll
     for (int k = 0; k < 8; k++) acc_enca[k] = 0.0f;
-    float acc_e2[4], acc_u2[8], acc_c2[3][16];   // weight gradients of the skinny output layers (lz_head_bwd.hip)
+    float acc_e2[4], acc_u2[8], acc_c2[3][16];   // weight gradients of the skinny output layers, per lane: feature 16 t + 4 q + r
 #pragma unroll
     for (int k = 0; k < 4; k++) acc_e2[k] = 0.0f;
 #pragma unroll
@@ -497,6 +404,17 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
             att16[1] = lz_v2u{h_cvt2(w1[0], w1[1], false), h_cvt2(w1[2], w1[3], false)};
         }
     };
+    // XYZ: the sink of the recomputed f32 chain -- the X half to the record as the recording forward stores it, the state row into `in`
+    struct XyzSink : LzRecSink<false> {
+        In& in;
+        __device__ __forceinline__ void st_att(const float (&v)[8]) { in.att0 = lz_v4{v[0], v[1], v[2], v[3]}; in.att1 = lz_v4{v[4], v[5], v[6], v[7]}; }
+        __device__ __forceinline__ void st_e1(const float (&v)[4]) { in.e = lz_v4{v[0], v[1], v[2], v[3]}; }
+        __device__ __forceinline__ void st_u1(const float (&v)[8]) { in.u0 = lz_v4{v[0], v[1], v[2], v[3]}; in.u1 = lz_v4{v[4], v[5], v[6], v[7]}; }
+        __device__ __forceinline__ void st_c1(const float (&v)[16]) {
+            in.c0 = lz_v4{v[0], v[1], v[2], v[3]}; in.c1 = lz_v4{v[4], v[5], v[6], v[7]};
+            in.c2 = lz_v4{v[8], v[9], v[10], v[11]}; in.c3 = lz_v4{v[12], v[13], v[14], v[15]};
+        }
+    };
     LzHead16Ctx hc16;
     if constexpr (RC) {
         hc16.wl = reinterpret_cast<const lz_h8*>(wl + FW16);
@@ -535,7 +453,7 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
     In nx;
     InRc nxr;
     if constexpr (RC) nxr = fetch_rc(slice);
-    else nx = fetch(slice);
+    else if constexpr (!XYZ) nx = fetch(slice);
     for (;;) {
         if constexpr (FUSE) {
             if ((uint32_t)(slice - wave) >= n_local) break;                     // workgroup-uniform: the round's first slice
@@ -556,6 +474,7 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
         RegSink rs;
         lz_v4 rc_bx0 = {0.0f, 0.0f, 0.0f, 0.0f};
         float rc_bx1 = 0.0f, rc_eyeatt = 0.0f;
+        LzFwd32Out fo;   // XYZ: the chain's masks and scalars
         if constexpr (RC) {
             // the forward of this slice again, from its enc_x operand: the layer inputs / state pairs land in `rs`, the scalars and masks in `fo`
             const InRc ir = nxr;
@@ -574,11 +493,27 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
             in.mk = lz_v4{__uint_as_float(fo.mk_a1 | (fo.mk_s1 << 16)), __uint_as_float(fo.mk_s2 | (fo.mk_c1 << 16)), __uint_as_float(fo.mk_u1 | (fo.mk_e1 << 8)), sc};
             in.clr = lz_v4{fo.cpre[0], fo.cpre[1], fo.cpre[2], 0.0f};
             in.g_sig = ir.g_sig; in.g_aa = ir.g_aa; in.g_ae = ir.g_ae; in.g_un = ir.g_un; in.g_r0 = ir.g_r0; in.g_r1 = ir.g_r1; in.g_r2 = ir.g_r2;
+        } else if constexpr (XYZ) {
+            // the forward of this slice again, from its positions: the X half of the record goes to memory, the state row into `in`
+            float encx[9];
+            lz_head_gather(hc.emb, hc.tab, st[row * 3], st[row * 3 + 1], st[row * 3 + 2], q, hc.bound, hc.two_bound, encx);
+            // every per-sample input is loaded here, before the first record store of the slice: a load issued after stores can only be
+            // waited for once those stores have been acknowledged (one counter, in order), which under this kernel's write stream takes microseconds
+            in.g_sig = A.g_sigma[row]; in.g_aa = A.g_amb_aud[row]; in.g_ae = A.g_amb_eye ? A.g_amb_eye[row] : 0.0f; in.g_un = A.g_unc[row];
+            in.g_r0 = A.g_rgb[row * 3]; in.g_r1 = A.g_rgb[row * 3 + 1]; in.g_r2 = A.g_rgb[row * 3 + 2];
+            const float d0 = A.dirs[row * 3], d1 = A.dirs[row * 3 + 1], d2 = A.dirs[row * 3 + 2];
+            __builtin_amdgcn_sched_barrier(0);
+            in.e = lz_v4{0.0f, 0.0f, 0.0f, 0.0f};   // (no eye input: no st_e1 call)
+            XyzSink xs{{rb, nullptr, q}, in};
+            lz_fwd32_chain(hc, lane, encx, d0, d1, d2, xs, fo);
+            // the state row's mask words; its four scalars are on every lane of the sample here and are taken from `fo` (no shuffle)
+            in.mk = lz_v4{__uint_as_float(fo.mk_a1 | (fo.mk_s1 << 16)), __uint_as_float(fo.mk_s2 | (fo.mk_c1 << 16)), __uint_as_float(fo.mk_u1 | (fo.mk_e1 << 8)), 0.0f};
+            in.clr = lz_v4{fo.cpre[0], fo.cpre[1], fo.cpre[2], 0.0f};
         } else {
             in = nx;
         }
         const int next = FUSE ? slice + 8 : grab();
-        if constexpr (!FUSE) nx = fetch(next);   // FUSE fetches later in the slice (after the sig0 segment): 51 registers less across the chain
+        if constexpr (!FUSE && !XYZ) nx = fetch(next);   // FUSE fetches later in the slice (after the sig0 segment): 51 registers less across the chain
         // FUSE helpers (all lanes take part in every LDS access: the transposing read needs EXEC all ones)
         float* const my_area0 = fuse + wave * AREA;
         auto g_put = [&](int tile, float v0, float v1, float v2, float v3) {     // this lane's four columns 4 q .. 4 q + 3 of a G tile
@@ -736,8 +671,8 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
         const uint32_t w0 = lz_fbits(l_mk[0]), w1 = lz_fbits(l_mk[1]), w2 = lz_fbits(l_mk[2]);
         const uint32_t mk_a1 = w0 & 0xffffu, mk_s1 = w0 >> 16, mk_s2 = w1 & 0xffffu, mk_c1 = w1 >> 16, mk_u1 = w2 & 0xffu, mk_e1 = (w2 >> 8) & 0xfu;
         // the four scalars sit one per q lane of the sample
-        const float norm = __shfl(l_mk[3], s, 64), eyeatt = __shfl(l_mk[3], s + 16, 64), upre = __shfl(l_mk[3], s + 32, 64),
-                    sigma = __shfl(l_mk[3], s + 48, 64);
+        const float norm = XYZ ? fo.norm : __shfl(l_mk[3], s, 64), eyeatt = XYZ ? fo.eyeatt : __shfl(l_mk[3], s + 16, 64),
+                    upre = XYZ ? fo.upre : __shfl(l_mk[3], s + 32, 64), sigma = XYZ ? fo.sigma : __shfl(l_mk[3], s + 48, 64);
 
         // uncertainty / colour heads: d loss / d pre-activation, and the skinny layers' weight gradients
         const float du = g_un * lz_sigmoidf(upre);
@@ -1112,6 +1047,31 @@ extern "C" int lz_triplane_head_backward_recorded(const lz_head_params* p, const
     else if (record_f16) hipLaunchKernelGGL((lz_k_triplane_head_backward_rec<true, false>), grid, block, 0, lz_st(stream), a, state, M, (float*)nullptr);
     else hipLaunchKernelGGL((lz_k_triplane_head_backward_rec<false, false>), grid, block, 0, lz_st(stream), a, state, M, (float*)nullptr);
     LZ_CHECK_LAUNCH("triplane_head_backward_recorded");
+    return LZ_OK;
+}
+
+// record=False of the f32 head: the forward (lz_triplane_head_forward) left nothing behind; this backward recomputes it from the
+// positions and view directions and writes the f32 records (both halves) that lz_triplane_head_grad_w reduces.
+extern "C" int lz_triplane_head_backward(const lz_head_params* p, const float* xyzs, const float* dirs, uint32_t M, const float* g_sigma,
+                                         const float* g_rgb, const float* g_amb_aud, const float* g_amb_eye, const float* g_unc,
+                                         const lz_head_bwd_out* out, lz_stream_t stream) {
+    LZ_REQUIRE(p && xyzs && dirs && g_sigma && g_rgb && g_amb_aud && g_unc && out, LZ_ERR_BAD_ARGUMENT, "triplane_head_backward: null tensor");
+    LZ_REQUIRE(p->emb_xy && p->emb_yz && p->emb_xz && p->offsets && p->packed && p->enc_a, LZ_ERR_BAD_ARGUMENT,
+               "triplane_head_backward: incomplete lz_head_params");
+    LZ_REQUIRE(p->precision == 0 && !p->testing, LZ_ERR_UNSUPPORTED, "triplane_head_backward: f32 training mode only");
+    const lz_head_bwd_out& o = *out;
+    LZ_REQUIRE(o.denc && o.small && o.rec, LZ_ERR_BAD_ARGUMENT, "triplane_head_backward: incomplete lz_head_bwd_out");
+    LZ_REQUIRE(((uintptr_t)o.rec & 15u) == 0, LZ_ERR_BAD_ARGUMENT, "triplane_head_backward: rec must be 16-byte aligned");
+    if (M == 0) return LZ_OK;
+    LzHeadBwdArgs a;
+    lz_fill_head_args(p, a.fwd);
+    a.g_sigma = g_sigma; a.g_rgb = g_rgb; a.g_amb_aud = g_amb_aud; a.g_amb_eye = g_amb_eye; a.g_unc = g_unc;
+    a.o = o;
+    a.wb16 = nullptr;
+    a.dirs = dirs;
+    hipLaunchKernelGGL((lz_k_triplane_head_backward_rec<false, false, false, true>), dim3(lz_rec_grid(M, LZ_BWD_WG)), dim3(LZ_BWD_WG), 0,
+                       lz_st(stream), a, xyzs, M, (float*)nullptr);
+    LZ_CHECK_LAUNCH("triplane_head_backward");
     return LZ_OK;
 }
 

@@ -481,8 +481,9 @@ def test_fused_train_head_tiny_batches(params, golden, M):
 @pytest.mark.parametrize("exp_eye,ind_dim", [(True, 4), (False, 0)])
 def test_fused_train_head_record_equals_recompute(params, golden, exp_eye, ind_dim):
     """record=True (forward writes the layer inputs and a state row, backward starts from them) against record=False (backward
-    recomputes the forward): same outputs bit for bit, the wide layers' weight gradients bit for bit (the per-sample records are the
-    same and their reduction is deterministic), everything that ends in float atomics to 1e-5 of its largest entry"""
+    recomputes the forward): same outputs bit for bit, d loss / d enc_x (last_denc: one plain store per sample) and the wide layers'
+    weight gradients bit for bit (the per-sample records are the same and their reduction is deterministic), everything that ends in
+    float atomics to 1e-5 of its largest entry"""
     from lzzx_nerf_amd.head_train import FusedTriplaneTrainHead
     rng = np.random.default_rng(11)
     p = dict(params)
@@ -496,6 +497,7 @@ def test_fused_train_head_record_equals_recompute(params, golden, exp_eye, ind_d
     res = []
     for record in (True, False):
         net = FusedTriplaneTrainHead(p, bound=1.0, exp_eye=exp_eye, ind_dim=ind_dim, record=record).cuda()
+        net.keep_denc = True
         enc_a = dev(golden["net_enc_a"]).requires_grad_(True)
         eye = dev(golden["net_eye"]) if exp_eye else None
         ind = dev(golden["net_ind"]).requires_grad_(True) if ind_dim else None
@@ -505,10 +507,12 @@ def test_fused_train_head_record_equals_recompute(params, golden, exp_eye, ind_d
         grads["enc_a"] = enc_a.grad
         if ind is not None:
             grads["ind"] = ind.grad
-        res.append(([o.detach() for o in outs], grads))
-    (o1, g1), (o2, g2) = res
+        res.append(([o.detach() for o in outs], grads, net.last_denc))
+    (o1, g1, denc1), (o2, g2, denc2) = res
     for a, b in zip(o1, o2):
         assert torch.equal(a, b)
+    assert denc1 is not None and denc1.shape == (3, 12, M)
+    assert torch.equal(denc1, denc2)
     assert g1.keys() == g2.keys()
     exact = ("aud_ch_att_net.net.0.weight", "aud_ch_att_net.net.1.weight", "sigma_net.net.0.weight", "sigma_net.net.1.weight", "unc_net.net.0.weight")
     for k in g1:
