@@ -22,7 +22,6 @@
 #include "lzzx_detmath.h"
 #include <hip/hip_fp16.h>
 #include <math.h>
-#include <stdlib.h>
 #include <type_traits>
 
 #define LZ_MAX_LEVELS 32
@@ -64,6 +63,129 @@ __device__ __forceinline__ uint32_t lz_grid_index(uint32_t C, uint32_t gridtype,
     return (index % hashmap_size) * C;
 }
 
+// ---- the arithmetic every kernel below shares: one level record, one cell, one corner ------------------------------
+// A level's mode says how a corner's index reaches the table, exactly as get_grid_index does it:
+//   0  dense: every stride fitted, so index < size and the modulo is the identity;
+//   1  hashed with a power-of-two table: the modulo is a mask;
+//   2  anything else: the generic (index % size) of lz_grid_index.
+// Two exclusions send a level to mode 2.  Very fine levels: the reference's uint32 stride wraps, and only the generic path keeps its
+// exact (index % size).  align_corners: side = res, so the +1 corner of x = 1 lands one stride past the level (gridencoder.cu:71
+// wraps it), and no level is dense.
+template <uint32_t D>
+__device__ __forceinline__ uint32_t lz_grid_level_mode(uint32_t hs, uint32_t res, uint32_t gridtype, bool align_corners) {
+    // replay the stride loop of get_grid_index (gridencoder.cu:56-69)
+    uint32_t stride = 1;
+    uint64_t stride_exact = 1;   // the same product without 32-bit wrap-around
+    for (uint32_t d = 0; d < D; d++)
+        if (stride <= hs) {
+            stride *= align_corners ? res : (res + 1);
+            stride_exact *= align_corners ? res : (res + 1);
+        }
+    const bool wrapped = stride_exact != (uint64_t)stride;
+    const bool hashed = gridtype == 0 && stride > hs;
+    const bool dense = stride <= hs && !wrapped && !align_corners;
+    const bool pow2 = (hs & (hs - 1u)) == 0u;
+    return dense ? 0u : ((hashed && pow2 && !wrapped) ? 1u : 2u);
+}
+
+struct LzGridLevel {
+    uint32_t off0, hs, res;   // first entry of the level, its size (entries), its resolution
+    float scale;
+    uint32_t mode;            // lz_grid_level_mode
+};
+
+// CLASSIFY = false puts every level in mode 2, which is exact for all of them: the one-lane-per-(sample, level) kernels that serve the
+// other layouts, dy_dx and the plain scatter keep a single index path (and their code size).
+template <uint32_t D, bool CLASSIFY = true>
+__device__ __forceinline__ LzGridLevel lz_grid_level(const int* __restrict__ offsets, const LzGridLevels& lv, uint32_t level,
+                                                     uint32_t gridtype, bool align_corners) {
+    LzGridLevel r;
+    r.off0 = (uint32_t)offsets[level];
+    r.hs = (uint32_t)offsets[level + 1] - r.off0;
+    r.res = lv.res[level];
+    r.scale = lv.scale[level];
+    r.mode = CLASSIFY ? lz_grid_level_mode<D>(r.hs, r.res, gridtype, align_corners) : 2u;
+    return r;
+}
+
+// The cell of x in a level: lower corner pg, fraction pos, and whether some x[d] lies outside [0, 1] (a NaN does not).  CLAMP clamps x
+// for addressing only, in the kernels that compute every row and write zeros for the out-of-range ones; the others skip those rows
+// before they touch the table, so they leave x as it is (which matters for a NaN).
+template <uint32_t D> struct LzGridCell {
+    uint32_t pg[D];
+    float pos[D];
+    bool oob;
+};
+template <uint32_t D, bool CLAMP>
+__device__ __forceinline__ LzGridCell<D> lz_grid_cell(const float (&x)[D], float scale, bool align_corners) {
+    LzGridCell<D> c;
+    c.oob = false;
+#pragma unroll
+    for (uint32_t d = 0; d < D; d++) {
+        if (x[d] < 0 || x[d] > 1) c.oob = true;
+        const float xc = CLAMP ? lz_fminf(lz_fmaxf(x[d], 0.0f), 1.0f) : x[d];
+        c.pos[d] = lz_fmaf(xc, scale, align_corners ? 0.0f : 0.5f);
+        c.pg[d] = (uint32_t)floorf(c.pos[d]);
+        c.pos[d] -= (float)c.pg[d];
+    }
+    return c;
+}
+
+// Weight of corner idx (bit d set: the upper corner in dimension d): the product over d in increasing order, starting from w.  The
+// forward's dy_dx starts from the level's scale and leaves out the dimension it differentiates (skip).
+template <uint32_t D>
+__device__ __forceinline__ float lz_grid_weight(const LzGridCell<D>& c, uint32_t idx, float w = 1.0f, uint32_t skip = D) {
+#pragma unroll
+    for (uint32_t d = 0; d < D; d++) {
+        if (d == skip) continue;
+        if ((idx & (1u << d)) == 0) w *= 1 - c.pos[d];
+        else w *= c.pos[d];
+    }
+    return w;
+}
+
+// Index terms per dimension for the dense (mode 0) and power-of-two hashed (mode 1) levels: term[d][0] belongs to the lower cell
+// coordinate pg[d], term[d][1] to pg[d] + 1 -- the lower one plus a constant modulo 2^32, exactly the reference's uint32 arithmetic
+// (gridencoder.cu:60-98: index += pos * stride / result ^= pos * prime).  A corner's index is then the sum (dense) or the xor (hashed)
+// of D terms: one 32-bit multiply per dimension and sample, spelled out (the compiler found the same common subexpressions in the
+// per-corner form: measured, no change in the triplane plane or the cfg2 gather -- neither is bound by the index arithmetic).
+// Mode 2 does not use them.
+template <uint32_t D>
+__device__ __forceinline__ void lz_grid_terms(const LzGridLevel& lvl, const LzGridCell<D>& c, bool align_corners, uint32_t (&term)[D][2]) {
+    constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
+    uint32_t stride = 1;
+#pragma unroll
+    for (uint32_t d = 0; d < D; d++) {
+        const uint32_t k = lvl.mode == 1u ? primes[d] : stride;
+        term[d][0] = d == 0 ? c.pg[d] : c.pg[d] * k;      // primes[0] == 1 and the first stride is 1
+        term[d][1] = term[d][0] + k;
+        stride *= align_corners ? lvl.res : (lvl.res + 1);
+    }
+}
+template <uint32_t D>
+__device__ __forceinline__ uint32_t lz_grid_corner(const uint32_t (&term)[D][2], uint32_t idx, uint32_t mode, uint32_t hs) {
+    uint32_t lin = 0, h = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < D; d++) {
+        const uint32_t t = term[d][(idx >> d) & 1u];
+        lin += t;
+        h ^= t;
+    }
+    return mode == 1u ? (h & (hs - 1u)) : lin;
+}
+// Element offset (index * C) of corner idx in the level's table, the same value in every mode
+template <uint32_t D>
+__device__ __forceinline__ uint32_t lz_grid_corner_index(const LzGridLevel& lvl, const LzGridCell<D>& c, const uint32_t (&term)[D][2],
+                                                         uint32_t idx, uint32_t C, uint32_t gridtype, bool align_corners) {
+    if (lvl.mode == 2u) {
+        uint32_t pl[D];
+#pragma unroll
+        for (uint32_t d = 0; d < D; d++) pl[d] = c.pg[d] + ((idx >> d) & 1u);
+        return lz_grid_index<D>(C, gridtype, align_corners, lvl.hs, lvl.res, pl);
+    }
+    return lz_grid_corner<D>(term, idx, lvl.mode, lvl.hs) * C;
+}
+
 template <typename T> struct LzElem;
 template <> struct LzElem<float> {
     static __device__ __forceinline__ float ld(const float* p) { return *p; }
@@ -102,14 +224,12 @@ lz_k_grid_forward(const float* __restrict__ inputs, const T* __restrict__ grid, 
     const size_t oidx = sample_major ? ((size_t)b * L + level) * C : ((size_t)level * B + b) * C;
     T* out = outputs + oidx;
 
+    const LzGridLevel lvl = lz_grid_level<D, false>(offsets, lv, level, gridtype, align_corners);
     float x[D];
-    bool oob = false;
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) oob = true;
-    }
-    if (oob) {  // gridencoder.cu:98-122
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+    if (cell.oob) {  // gridencoder.cu:98-122
 #pragma unroll
         for (uint32_t ch = 0; ch < C; ch++) out[ch] = LzElem<T>::st(0.0f);
         if (dy_dx) {
@@ -119,33 +239,16 @@ lz_k_grid_forward(const float* __restrict__ inputs, const T* __restrict__ grid, 
         }
         return;
     }
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    const float scale = lv.scale[level];
-    const uint32_t resolution = lv.res[level];
-    const T* g = grid + (size_t)off0 * C;
-
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = lz_fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    const T* g = grid + (size_t)lvl.off0 * C;
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
     float res[C];
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++) res[ch] = 0.0f;
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1.0f;
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        const uint32_t index = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);
+        const float w = lz_grid_weight<D>(cell, idx);
+        const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);
 #pragma unroll
         for (uint32_t ch = 0; ch < C; ch++) res[ch] = LzElem<T>::acc(res[ch], w, LzElem<T>::ld(g + index + ch));
     }
@@ -161,18 +264,11 @@ lz_k_grid_forward(const float* __restrict__ inputs, const T* __restrict__ grid, 
             for (uint32_t ch = 0; ch < C; ch++) rg[ch] = 0.0f;
 #pragma unroll
             for (uint32_t idx = 0; idx < (1u << (D - 1)); idx++) {
-                float w = scale;
-                uint32_t pl[D];
-#pragma unroll
-                for (uint32_t nd = 0; nd < D - 1; nd++) {
-                    const uint32_t d = (nd >= gd) ? (nd + 1) : nd;
-                    if ((idx & (1u << nd)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-                    else { w *= pos[d]; pl[d] = pg[d] + 1; }
-                }
-                pl[gd] = pg[gd];
-                const uint32_t il = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);
-                pl[gd] = pg[gd] + 1;
-                const uint32_t ir = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);
+                // the lower corner along gd: bit gd of the corner clear, the other D - 1 bits taken from idx in order
+                const uint32_t lo = (idx & ((1u << gd) - 1u)) | ((idx >> gd) << (gd + 1));
+                const float w = lz_grid_weight<D>(cell, lo, lvl.scale, gd);
+                const uint32_t il = lz_grid_corner_index<D>(lvl, cell, term, lo, C, gridtype, align_corners);
+                const uint32_t ir = lz_grid_corner_index<D>(lvl, cell, term, lo | (1u << gd), C, gridtype, align_corners);
 #pragma unroll
                 for (uint32_t ch = 0; ch < C; ch++)
                     rg[ch] = LzElem<T>::accd(rg[ch], w, LzElem<T>::ld(g + ir + ch), LzElem<T>::ld(g + il + ch));
@@ -192,99 +288,46 @@ template <typename T, uint32_t D, uint32_t C>
 __global__ void __launch_bounds__(256)
 lz_k_grid_forward_sm(const float* __restrict__ inputs, const T* __restrict__ grid, const int* __restrict__ offsets,
                      T* __restrict__ outputs, uint32_t B, uint32_t L, LzGridLevels lv, uint32_t gridtype, bool align_corners) {
-    __shared__ float s_scale[LZ_MAX_LEVELS];
-    __shared__ uint32_t s_res[LZ_MAX_LEVELS], s_off[LZ_MAX_LEVELS], s_hs[LZ_MAX_LEVELS], s_mode[LZ_MAX_LEVELS];
+    __shared__ LzGridLevel s_lvl[LZ_MAX_LEVELS];
     const uint32_t tid = threadIdx.y * blockDim.x + threadIdx.x;
-    if (tid < L) {
-        const uint32_t off0 = (uint32_t)offsets[tid], hs = (uint32_t)offsets[tid + 1] - off0;
-        const uint32_t res = lv.res[tid];
-        // replay the stride loop of get_grid_index (gridencoder.cu:56-69) once per level
-        uint32_t stride = 1;
-        uint64_t stride_exact = 1;   // the same product without 32-bit wrap-around
-        for (uint32_t d = 0; d < D; d++)
-            if (stride <= hs) {
-                stride *= align_corners ? res : (res + 1);
-                stride_exact *= align_corners ? res : (res + 1);
-            }
-        const bool wrapped = stride_exact != (uint64_t)stride;   // very fine levels: the reference's uint32 stride wraps; keep
-                                                                  // its exact (index % size) behaviour via the generic path
-        const bool hashed = gridtype == 0 && stride > hs;
-        const bool dense = stride <= hs && !wrapped && !align_corners;   // every stride fitted: index < hs, modulo is the identity --
-                                                                  // not with align_corners: side = res, and the +1 corner of x = 1
-                                                                  // lands one stride past the level (gridencoder.cu:71 wraps it)
-        const bool pow2 = (hs & (hs - 1u)) == 0u;
-        s_scale[tid] = lv.scale[tid];
-        s_res[tid] = res; s_off[tid] = off0; s_hs[tid] = hs;
-        // 0 none, 1 mask, 2 modulo; bit 2: hash
-        s_mode[tid] = dense ? 0u : ((pow2 && !wrapped) ? 1u : 2u) | (hashed ? 4u : 0u);
-    }
+    if (tid < L) s_lvl[tid] = lz_grid_level<D>(offsets, lv, tid, gridtype, align_corners);
     __syncthreads();
     const uint32_t level = threadIdx.x;
     const uint32_t b = blockIdx.x * blockDim.y + threadIdx.y;
     if (b >= B) return;
     T* out = outputs + ((size_t)b * L + level) * C;
     float x[D];
-    bool oob = false;
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) oob = true;
-    }
-    const uint32_t hashmap_size = s_hs[level], resolution = s_res[level], mode = s_mode[level];
-    const float scale = s_scale[level];
-    const T* g = grid + (size_t)s_off[level] * C;
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const float xc = lz_fminf(lz_fmaxf(x[d], 0.0f), 1.0f);   // clamp for addressing only; result zeroed below
-        pos[d] = lz_fmaf(xc, scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridLevel lvl = s_lvl[level];
+    const T* g = grid + (size_t)lvl.off0 * C;
+    const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);   // result zeroed below when out of range
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
     float res[C];
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++) res[ch] = 0.0f;
-    const bool slow = __any((mode & 3u) == 2u);
+    // The fast path runs only when every level of the wave is dense, or hashed with a power-of-two table and no wrapped stride: no
+    // mode 2, so it leaves the generic modulo out.  Otherwise every lane takes mode 2, which is exact for every level.
+    const LzGridLevel generic = {lvl.off0, lvl.hs, lvl.res, lvl.scale, 2u};
     auto corners = [&](auto slow_tag) {
         constexpr bool SLOW = decltype(slow_tag)::value;
 #pragma unroll
         for (uint32_t idx = 0; idx < (1u << D); idx++) {
-            float w = 1.0f;
-            uint32_t pl[D];
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-                else { w *= pos[d]; pl[d] = pg[d] + 1; }
-            }
-            uint32_t index;
-            if constexpr (SLOW) {
-                index = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);
-            } else {
-                constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
-                uint32_t lin = 0, h = 0, stride = 1;
-#pragma unroll
-                for (uint32_t d = 0; d < D; d++) {
-                    lin += pl[d] * stride;            // only used when every stride fitted (mode 0)
-                    stride *= align_corners ? resolution : (resolution + 1);
-                    h ^= pl[d] * primes[d];
-                }
-                // mode 0: dense.  mode 1|4: hashed, power-of-two table.  (mode 1 without hash = tiled wrap of a partial
-                // sum: routed to the generic path by `slow` below)
-                index = ((mode & 4u) ? (h & (hashmap_size - 1u)) : lin) * C;
-            }
+            const float w = lz_grid_weight<D>(cell, idx);
+            const uint32_t index = SLOW ? lz_grid_corner_index<D>(generic, cell, term, idx, C, gridtype, align_corners)
+                                        : lz_grid_corner<D>(term, idx, lvl.mode, lvl.hs) * C;
 #pragma unroll
             for (uint32_t ch = 0; ch < C; ch++) res[ch] = LzElem<T>::acc(res[ch], w, LzElem<T>::ld(g + index + ch));
         }
     };
-    // generic path when some level needs a true modulo, or wraps a partial (tiled) sum
-    if (slow || __any(mode != 0u && (mode & 4u) == 0u)) corners(std::true_type{});
+    if (__any(lvl.mode == 2u)) corners(std::true_type{});
     else corners(std::false_type{});
     if constexpr (C == 2 && sizeof(T) == 4) {
-        *reinterpret_cast<float2*>(out) = oob ? make_float2(0.f, 0.f) : make_float2(res[0], res[1]);
+        *reinterpret_cast<float2*>(out) = cell.oob ? make_float2(0.f, 0.f) : make_float2(res[0], res[1]);
     } else {
 #pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) out[ch] = LzElem<T>::st(oob ? 0.0f : res[ch]);
+        for (uint32_t ch = 0; ch < C; ch++) out[ch] = LzElem<T>::st(cell.oob ? 0.0f : res[ch]);
     }
 }
 
@@ -296,30 +339,21 @@ lz_k_grid_corner_indices(const float* __restrict__ inputs, const int* __restrict
     const uint32_t level = blockIdx.y;
     if (b >= B) return;
     int* o = out + ((size_t)level * B + b) * (1u << D);
+    const LzGridLevel lvl = lz_grid_level<D, false>(offsets, lv, level, gridtype, align_corners);
     float x[D];
-    bool oob = false;
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) oob = true;
-    }
-    if (oob) {
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+    if (cell.oob) {
 #pragma unroll
         for (uint32_t i = 0; i < (1u << D); i++) o[i] = -1;
         return;
     }
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    uint32_t pg[D];
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) pg[d] = (uint32_t)floorf(lz_fmaf(x[d], lv.scale[level], align_corners ? 0.0f : 0.5f));
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) pl[d] = pg[d] + ((idx >> d) & 1u);
-        o[idx] = (int)(off0 * C + lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, lv.res[level], pl));
-    }
+    for (uint32_t idx = 0; idx < (1u << D); idx++)
+        o[idx] = (int)(lvl.off0 * C + lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners));
 }
 
 // ---- backward: scatter-add of w * grad into the table (gridencoder.cu:226-313) ----
@@ -341,40 +375,23 @@ lz_k_grid_backward(const T* __restrict__ grad, const float* __restrict__ inputs,
         level = blockIdx.y;
         if (b >= B) return;
     }
+    const LzGridLevel lvl = lz_grid_level<D, false>(offsets, lv, level, gridtype, align_corners);
     float x[D];
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) return;
-    }
-    const uint32_t off0 = (uint32_t)offsets[level];
-    const uint32_t hashmap_size = (uint32_t)offsets[level + 1] - off0;
-    const float scale = lv.scale[level];
-    const uint32_t resolution = lv.res[level];
-    T* gg = grad_grid + (size_t)off0 * C;
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+    if (cell.oob) return;
+    T* gg = grad_grid + (size_t)lvl.off0 * C;
     const T* gsrc = grad + (sample_major ? ((size_t)b * L + level) * C : ((size_t)level * B + b) * C);
     float gcur[C];
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++) gcur[ch] = LzElem<T>::ld(gsrc + ch);
-
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = lz_fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1.0f;
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        const uint32_t index = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);
+        const float w = lz_grid_weight<D>(cell, idx);
+        const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);
         if constexpr (sizeof(T) == 4) {
 #pragma unroll
             for (uint32_t ch = 0; ch < C; ch++) lz_atomic_add(reinterpret_cast<float*>(gg) + index + ch, w * gcur[ch]);
@@ -421,37 +438,20 @@ lz_k_grid_backward_xc(const float* __restrict__ grad, const float* __restrict__ 
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t b = t / LPS, sub = t - b * LPS, xb = sub / C, ch = sub - xb * C;
     if (b >= B) return;
+    const LzGridLevel lvl = lz_grid_level<D, false>(offsets, lv, level, gridtype, align_corners);
     float x[D];
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) return;
-    }
-    const uint32_t off0 = (uint32_t)offsets[level], hs = (uint32_t)offsets[level + 1] - off0;
-    const float scale = lv.scale[level];
-    const uint32_t resolution = lv.res[level];
-    float* gg = grad_grid + (size_t)off0 * C;
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+    if (cell.oob) return;
+    float* gg = grad_grid + (size_t)lvl.off0 * C;
     const float g = grad[(sample_major ? ((size_t)b * L + level) * C : ((size_t)level * B + b) * C) + ch];
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = lz_fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
     for (uint32_t h = 0; h < (1u << (D - 1)); h++) {
         const uint32_t idx = (h << 1) | xb;
-        float w = 1.0f;
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-            else { w *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        const uint32_t index = lz_grid_index<D>(C, gridtype, align_corners, hs, resolution, pl);
-        lz_atomic_add(gg + index + ch, w * g);
+        lz_atomic_add(gg + lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners) + ch, lz_grid_weight<D>(cell, idx) * g);
     }
 }
 
@@ -486,95 +486,41 @@ lz_k_grid_input_backward(const T* __restrict__ grad, const T* __restrict__ dy_dx
 // to each other in dispatch order, so their partial-line stores merge in that XCD's L2 before write-back.
 // A level that does not fit LDS falls back to global gathers inside the same kernel (wave-uniform branch).
 #define LZ_GRID_LDS_BYTES 65536
+#define LZ_GRID_LDS_WG 512
+#define LZ_GRID_LDS_CHUNK 32768
 
-// Index terms per dimension for the dense (mode 0) and power-of-two hashed (mode 1) levels: term[d][0] belongs to the lower cell
-// coordinate pg[d], term[d][1] to pg[d] + 1 -- the lower one plus a constant modulo 2^32, exactly the reference's uint32 arithmetic
-// (gridencoder.cu:60-98: index += pos * stride / result ^= pos * prime).  A corner's index is then the sum (dense) or the xor (hashed)
-// of D terms: one 32-bit multiply per dimension and sample, spelled out (the compiler found the same common subexpressions in the
-// per-corner form: measured, no change in the triplane plane or the cfg2 gather -- neither is bound by the index arithmetic).
-template <uint32_t D>
-__device__ __forceinline__ void lz_grid_terms(const uint32_t (&pg)[D], uint32_t mode, uint32_t resolution, bool align_corners, uint32_t (&term)[D][2]) {
-    constexpr uint32_t primes[7] = {1u, 2654435761u, 805459861u, 3674653429u, 2097192037u, 1434869437u, 2165219737u};
-    uint32_t stride = 1;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const uint32_t k = mode == 1u ? primes[d] : stride;
-        term[d][0] = d == 0 ? pg[d] : pg[d] * k;      // primes[0] == 1 and the first stride is 1
-        term[d][1] = term[d][0] + k;
-        stride *= align_corners ? resolution : (resolution + 1);
-    }
-}
-template <uint32_t D>
-__device__ __forceinline__ uint32_t lz_grid_corner(const uint32_t (&term)[D][2], uint32_t idx, uint32_t mode, uint32_t hs) {
-    uint32_t lin = 0, h = 0;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const uint32_t t = term[d][(idx >> d) & 1u];
-        lin += t;
-        h ^= t;
-    }
-    return mode == 1u ? (h & (hs - 1u)) : lin;
-}
-
-template <typename T, uint32_t D, uint32_t C, bool IN_LDS>
+// tab: the level's table, in LDS or in global memory; lvl.mode is workgroup-uniform
+template <typename T, uint32_t D, uint32_t C>
 __device__ __forceinline__ void lz_grid_level_stream(const float* __restrict__ inputs, const T* __restrict__ tab, T* __restrict__ outputs,
-                                                     uint32_t b0, uint32_t b1, uint32_t L, uint32_t level, float scale,
-                                                     uint32_t resolution, uint32_t hashmap_size, uint32_t mode, uint32_t gridtype,
-                                                     bool align_corners) {
+                                                     uint32_t b0, uint32_t b1, uint32_t L, uint32_t level, const LzGridLevel& lvl,
+                                                     uint32_t gridtype, bool align_corners) {
     for (uint32_t b = b0 + threadIdx.x; b < b1; b += blockDim.x) {
         float x[D];
-        bool oob = false;
 #pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            x[d] = inputs[(size_t)b * D + d];
-            if (x[d] < 0 || x[d] > 1) oob = true;
-        }
-        float pos[D];
-        uint32_t pg[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            const float xc = lz_fminf(lz_fmaxf(x[d], 0.0f), 1.0f);
-            pos[d] = lz_fmaf(xc, scale, align_corners ? 0.0f : 0.5f);
-            pg[d] = (uint32_t)floorf(pos[d]);
-            pos[d] -= (float)pg[d];
-        }
+        for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+        const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);
         float res[C];
 #pragma unroll
         for (uint32_t ch = 0; ch < C; ch++) res[ch] = 0.0f;
-        // per-dimension index terms (lz_grid_terms)
         uint32_t term[D][2];
-        if (mode != 2u) lz_grid_terms<D>(pg, mode, resolution, align_corners, term);
+        lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
         for (uint32_t idx = 0; idx < (1u << D); idx++) {
-            float w = 1.0f;
-            uint32_t pl[D];
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-                else { w *= pos[d]; pl[d] = pg[d] + 1; }
-            }
-            uint32_t index;
-            if (mode == 2u) index = lz_grid_index<D>(C, gridtype, align_corners, hashmap_size, resolution, pl);   // workgroup-uniform: true modulo / wrapped strides
-            else index = lz_grid_corner<D>(term, idx, mode, hashmap_size) * C;
+            const float w = lz_grid_weight<D>(cell, idx);
+            const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);
 #pragma unroll
             for (uint32_t ch = 0; ch < C; ch++) res[ch] = LzElem<T>::acc(res[ch], w, LzElem<T>::ld(tab + index + ch));
         }
         T* out = outputs + ((size_t)b * L + level) * C;
         if constexpr (C == 2 && sizeof(T) == 4) {
-            *reinterpret_cast<float2*>(out) = oob ? make_float2(0.f, 0.f) : make_float2(res[0], res[1]);
+            *reinterpret_cast<float2*>(out) = cell.oob ? make_float2(0.f, 0.f) : make_float2(res[0], res[1]);
         } else {
 #pragma unroll
-            for (uint32_t ch = 0; ch < C; ch++) out[ch] = LzElem<T>::st(oob ? 0.0f : res[ch]);
+            for (uint32_t ch = 0; ch < C; ch++) out[ch] = LzElem<T>::st(cell.oob ? 0.0f : res[ch]);
         }
     }
 }
 
-#ifndef LZ_GRID_LDS_WG
-#define LZ_GRID_LDS_WG 512
-#endif
-#ifndef LZ_GRID_LDS_CHUNK
-#define LZ_GRID_LDS_CHUNK 32768
-#endif
 template <typename T, uint32_t D, uint32_t C>
 __global__ void __launch_bounds__(LZ_GRID_LDS_WG)
 lz_k_grid_forward_lds(const float* __restrict__ inputs, const T* __restrict__ grid, const int* __restrict__ offsets,
@@ -586,25 +532,9 @@ lz_k_grid_forward_lds(const float* __restrict__ inputs, const T* __restrict__ gr
     const uint32_t level = t % L, g = t / L;
     const uint32_t c = 8u * g + r;
     if (c >= n_chunks) return;
-    const uint32_t off0 = (uint32_t)offsets[level], hs = (uint32_t)offsets[level + 1] - off0;
-    const uint32_t res = lv.res[level];
-    const float scale = lv.scale[level];
-    // classify the level exactly like lz_k_grid_forward_sm: 0 dense (index < size), 1 hashed + power-of-two size (mask),
-    // 2 anything else (generic modulo path)
-    uint32_t stride = 1;
-    uint64_t stride_exact = 1;
-    for (uint32_t d = 0; d < D; d++)
-        if (stride <= hs) {
-            stride *= align_corners ? res : (res + 1);
-            stride_exact *= align_corners ? res : (res + 1);
-        }
-    const bool wrapped = stride_exact != (uint64_t)stride;
-    const bool hashed = gridtype == 0 && stride > hs;
-    const bool dense = stride <= hs && !wrapped && !align_corners;   // align_corners: the +1 corner of x = 1 needs the wrap
-    const bool pow2 = (hs & (hs - 1u)) == 0u;
-    const uint32_t mode = dense ? 0u : ((hashed && pow2 && !wrapped) ? 1u : 2u);
-    const T* gsrc = grid + (size_t)off0 * C;
-    const size_t bytes = (size_t)hs * C * sizeof(T);
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
+    const T* gsrc = grid + (size_t)lvl.off0 * C;
+    const size_t bytes = (size_t)lvl.hs * C * sizeof(T);
     const uint32_t b0 = c * chunk, b1 = (b0 + chunk < B) ? b0 + chunk : B;
     if (bytes <= LZ_GRID_LDS_BYTES) {
         // (off0 * C * sizeof(T)) is a multiple of 16: level sizes are multiples of 8 entries (grid.py:117)
@@ -612,11 +542,11 @@ lz_k_grid_forward_lds(const float* __restrict__ inputs, const T* __restrict__ gr
         uint4* d4 = reinterpret_cast<uint4*>(tab);
         const uint32_t n16 = (reinterpret_cast<uintptr_t>(gsrc) & 15u) ? 0u : (uint32_t)(bytes >> 4);
         for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) d4[i] = s4[i];
-        for (uint32_t i = (n16 << 4) / sizeof(T) + threadIdx.x; i < hs * C; i += blockDim.x) tab[i] = gsrc[i];
+        for (uint32_t i = (n16 << 4) / sizeof(T) + threadIdx.x; i < lvl.hs * C; i += blockDim.x) tab[i] = gsrc[i];
         __syncthreads();
-        lz_grid_level_stream<T, D, C, true>(inputs, tab, outputs, b0, b1, L, level, scale, res, hs, mode, gridtype, align_corners);
+        lz_grid_level_stream<T, D, C>(inputs, tab, outputs, b0, b1, L, level, lvl, gridtype, align_corners);
     } else {
-        lz_grid_level_stream<T, D, C, false>(inputs, gsrc, outputs, b0, b1, L, level, scale, res, hs, mode, gridtype, align_corners);
+        lz_grid_level_stream<T, D, C>(inputs, gsrc, outputs, b0, b1, L, level, lvl, gridtype, align_corners);
     }
 }
 
@@ -641,22 +571,6 @@ static void lz_grid_lds_launch(const float* inputs, const T* emb, const int* off
 //     [tile][level][sample in tile][C]          (tile = Tn samples; same bytes as the tile's final [sample][level][C])
 // and lz_k_grid_untile then transposes every tile in place through LDS (one workgroup owns one tile: load all, barrier,
 // store all).  The untile pass costs one read + one write of the output (~0.3 ms per GB), far less than it saves.
-template <uint32_t D>
-__device__ __forceinline__ uint32_t lz_grid_level_mode(uint32_t hs, uint32_t res, uint32_t gridtype, bool align_corners) {
-    uint32_t stride = 1;
-    uint64_t stride_exact = 1;
-    for (uint32_t d = 0; d < D; d++)
-        if (stride <= hs) {
-            stride *= align_corners ? res : (res + 1);
-            stride_exact *= align_corners ? res : (res + 1);
-        }
-    const bool wrapped = stride_exact != (uint64_t)stride;
-    const bool hashed = gridtype == 0 && stride > hs;
-    const bool dense = stride <= hs && !wrapped && !align_corners;   // align_corners: the +1 corner of x = 1 needs the wrap
-    const bool pow2 = (hs & (hs - 1u)) == 0u;
-    return dense ? 0u : ((hashed && pow2 && !wrapped) ? 1u : 2u);   // 0 identity, 1 hash + mask, 2 generic modulo
-}
-
 template <typename T, uint32_t C> struct LzVec {
     T v[C];
 };
@@ -670,43 +584,20 @@ lz_k_grid_forward_lm(const float* __restrict__ inputs, const T* __restrict__ gri
     const uint32_t n = (B - b0 < Tn) ? B - b0 : Tn;
     if (t >= n) return;
     const uint32_t b = b0 + t;
-    const uint32_t off0 = (uint32_t)offsets[level], hs = (uint32_t)offsets[level + 1] - off0;
-    const uint32_t resolution = lv.res[level];
-    const float scale = lv.scale[level];
-    const uint32_t mode = lz_grid_level_mode<D>(hs, resolution, gridtype, align_corners);
-    const T* g = grid + (size_t)off0 * C;
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
+    const T* g = grid + (size_t)lvl.off0 * C;
     float x[D];
-    bool oob = false;
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (x[d] < 0 || x[d] > 1) oob = true;
-    }
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const float xc = lz_fminf(lz_fmaxf(x[d], 0.0f), 1.0f);   // clamp for addressing only; result zeroed below
-        pos[d] = lz_fmaf(xc, scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);   // result zeroed below when out of range
     uint32_t index[1u << D];
     float w[1u << D];
     uint32_t term[D][2];
-    if (mode != 2u) lz_grid_terms<D>(pg, mode, resolution, align_corners, term);
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float wc = 1.0f;
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            if ((idx & (1u << d)) == 0) { wc *= 1 - pos[d]; pl[d] = pg[d]; }
-            else { wc *= pos[d]; pl[d] = pg[d] + 1; }
-        }
-        w[idx] = wc;
-        if (mode == 2u) index[idx] = lz_grid_index<D>(C, gridtype, align_corners, hs, resolution, pl);   // workgroup-uniform
-        else index[idx] = lz_grid_corner<D>(term, idx, mode, hs) * C;
+        w[idx] = lz_grid_weight<D>(cell, idx);
+        index[idx] = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);   // lvl.mode: workgroup-uniform
     }
     // all 2^D corner reads in flight before the first use; (index * sizeof(T)) is a multiple of the vector size
     LzVec<T, C> cv[1u << D];
@@ -722,7 +613,7 @@ lz_k_grid_forward_lm(const float* __restrict__ inputs, const T* __restrict__ gri
         for (uint32_t ch = 0; ch < C; ch++) res[ch] = LzElem<T>::acc(res[ch], w[idx], LzElem<T>::ld(&cv[idx].v[ch]));
     LzVec<T, C> o;
 #pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) o.v[ch] = LzElem<T>::st(oob ? 0.0f : res[ch]);
+    for (uint32_t ch = 0; ch < C; ch++) o.v[ch] = LzElem<T>::st(cell.oob ? 0.0f : res[ch]);
     T* out = outputs + ((size_t)b0 * L + (size_t)level * n + t) * C;
     __builtin_memcpy(__builtin_assume_aligned(out, sizeof(T) * C), &o, sizeof(T) * C);
 }
@@ -747,40 +638,21 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
     const uint32_t n = (B - b0 < Tn) ? B - b0 : Tn;
     if (t >= n) return;   // pair-uniform
     const uint32_t b = b0 + t;
-    const uint32_t off0 = (uint32_t)offsets[level], hs = (uint32_t)offsets[level + 1] - off0;
-    const uint32_t resolution = lv.res[level];
-    const float scale = lv.scale[level];
-    const uint32_t mode = lz_grid_level_mode<D>(hs, resolution, gridtype, align_corners);
-    const T* g = grid + (size_t)off0 * C;
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
+    const T* g = grid + (size_t)lvl.off0 * C;
     float x[D];
-    bool oob = false;
 #pragma unroll
     for (uint32_t d = 0; d < D; d++) {
         x[d] = inputs[(size_t)b * D + d];
         if (bound > 0.0f) x[d] = (x[d] + bound) / (2.0f * bound);
-        if (x[d] < 0 || x[d] > 1) oob = true;
     }
-    float pos[D];
-    uint32_t pg[D];
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        const float xc = lz_fminf(lz_fmaxf(x[d], 0.0f), 1.0f);
-        pos[d] = lz_fmaf(xc, scale, align_corners ? 0.0f : 0.5f);
-        pg[d] = (uint32_t)floorf(pos[d]);
-        pos[d] -= (float)pg[d];
-    }
+    const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);   // result zeroed below when out of range
     uint32_t own[NC][WORDS], oth[NC][WORDS];
     uint32_t term[D][2];
-    if (mode != 2u) lz_grid_terms<D>(pg, mode, resolution, align_corners, term);
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
     for (uint32_t h = 0; h < NC; h++) {
-        const uint32_t idx = (h << 1) | xb;
-        uint32_t pl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) pl[d] = pg[d] + ((idx >> d) & 1u);
-        uint32_t index;
-        if (mode == 2u) index = lz_grid_index<D>(C, gridtype, align_corners, hs, resolution, pl);
-        else index = lz_grid_corner<D>(term, idx, mode, hs) * C;
+        const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, (h << 1) | xb, C, gridtype, align_corners);
         __builtin_memcpy(own[h], __builtin_assume_aligned(g + index, sizeof(T) * C), sizeof(T) * C);
     }
 #pragma unroll
@@ -793,9 +665,7 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
     for (uint32_t ch = 0; ch < C; ch++) res[ch] = 0.0f;
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float wc = 1.0f;
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) wc *= ((idx & (1u << d)) == 0) ? 1 - pos[d] : pos[d];
+        const float wc = lz_grid_weight<D>(cell, idx);
         LzVec<T, C> cvv;
         __builtin_memcpy(&cvv, (idx & 1u) ? oth[idx >> 1] : own[idx >> 1], sizeof(T) * C);
 #pragma unroll
@@ -803,7 +673,7 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
     }
     LzVec<T, C> o;
 #pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) o.v[ch] = LzElem<T>::st(oob ? 0.0f : res[ch]);
+    for (uint32_t ch = 0; ch < C; ch++) o.v[ch] = LzElem<T>::st(cell.oob ? 0.0f : res[ch]);
     T* out = outputs + ((size_t)b0 * L + (size_t)level * n + t) * C;
     __builtin_memcpy(__builtin_assume_aligned(out, sizeof(T) * C), &o, sizeof(T) * C);
 }
@@ -890,51 +760,29 @@ static void lz_grid_lm_launch(const float* inputs, const T* emb, const int* offs
 // workgroup owns ONE (level, sample chunk): it zeroes a private copy, accumulates its chunk with LDS atomics (see below),
 // then flushes the non-zero entries with CONTIGUOUS global atomics (whole-line wave instructions: full atomic rate).
 // Summation order differs from the plain kernel (as it does between two runs of the reference); results agree to rounding.
-template <uint32_t D, uint32_t C, bool IN_LDS>
+// The global float-atomic scatter of one (level, chunk): levels too big for the LDS accumulator, and chunks with non-finite gradients
+template <uint32_t D, uint32_t C>
 __device__ __forceinline__ void lz_grid_level_scatter(const float* __restrict__ grad, const float* __restrict__ inputs, float* dst,
-                                                      uint32_t b0, uint32_t b1, uint32_t B, uint32_t L, uint32_t level, float scale,
-                                                      uint32_t resolution, uint32_t hs, uint32_t mode, uint32_t gridtype,
-                                                      bool align_corners, bool sample_major) {
+                                                      uint32_t b0, uint32_t b1, uint32_t B, uint32_t L, uint32_t level,
+                                                      const LzGridLevel& lvl, uint32_t gridtype, bool align_corners, bool sample_major) {
     for (uint32_t b = b0 + threadIdx.x; b < b1; b += blockDim.x) {
         float x[D];
-        bool oob = false;
 #pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            x[d] = inputs[(size_t)b * D + d];
-            if (x[d] < 0 || x[d] > 1) oob = true;
-        }
-        if (oob) continue;
+        for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+        const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+        if (cell.oob) continue;
         const float* gsrc = grad + (sample_major ? ((size_t)b * L + level) * C : ((size_t)level * B + b) * C);
         float gcur[C];
 #pragma unroll
         for (uint32_t ch = 0; ch < C; ch++) gcur[ch] = gsrc[ch];
-        float pos[D];
-        uint32_t pg[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            pos[d] = lz_fmaf(x[d], scale, align_corners ? 0.0f : 0.5f);
-            pg[d] = (uint32_t)floorf(pos[d]);
-            pos[d] -= (float)pg[d];
-        }
         uint32_t term[D][2];
-        if (mode != 2u) lz_grid_terms<D>(pg, mode, resolution, align_corners, term);
+        lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
         for (uint32_t idx = 0; idx < (1u << D); idx++) {
-            float w = 1.0f;
-            uint32_t pl[D];
+            const float w = lz_grid_weight<D>(cell, idx);
+            const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);
 #pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-                else { w *= pos[d]; pl[d] = pg[d] + 1; }
-            }
-            uint32_t index;
-            if (mode == 2u) index = lz_grid_index<D>(C, gridtype, align_corners, hs, resolution, pl);
-            else index = lz_grid_corner<D>(term, idx, mode, hs) * C;
-#pragma unroll
-            for (uint32_t ch = 0; ch < C; ch++) {
-                if constexpr (IN_LDS) __hip_atomic_fetch_add(dst + index + ch, w * gcur[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                else lz_atomic_add(dst + index + ch, w * gcur[ch]);
-            }
+            for (uint32_t ch = 0; ch < C; ch++) lz_atomic_add(dst + index + ch, w * gcur[ch]);
         }
     }
 }
@@ -962,15 +810,12 @@ lz_k_grid_backward_lds_fx(const float* __restrict__ grad, const float* __restric
     extern __shared__ __align__(16) unsigned long long lz_grid_acc64[];
     __shared__ float wmax[16];
     const uint32_t level = blockIdx.x % L, c = blockIdx.x / L;
-    const uint32_t off0 = (uint32_t)offsets[level], hs = (uint32_t)offsets[level + 1] - off0;
-    const uint32_t res = lv.res[level];
-    const float scale_l = lv.scale[level];
-    const uint32_t mode = lz_grid_level_mode<D>(hs, res, gridtype, align_corners);
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
     const uint32_t b0 = c * chunk, b1 = (B - b0 < chunk) ? B : b0 + chunk;
-    float* gg = grad_grid + (size_t)off0 * C;
-    const uint32_t n = hs * C;
+    float* gg = grad_grid + (size_t)lvl.off0 * C;
+    const uint32_t n = lvl.hs * C;
     if ((size_t)n * 8 > LZ_GRID_FX_LDS_BYTES) {
-        lz_grid_level_scatter<D, C, false>(grad, inputs, gg, b0, b1, B, L, level, scale_l, res, hs, mode, gridtype, align_corners, sample_major);
+        lz_grid_level_scatter<D, C>(grad, inputs, gg, b0, b1, B, L, level, lvl, gridtype, align_corners, sample_major);
         return;
     }
     // pass 1: largest |grad| of this (level, chunk).  For C == 1 (the triplane planes) a thread keeps its <= LZ_GRID_FX_KEEP gradients in
@@ -1024,7 +869,7 @@ lz_k_grid_backward_lds_fx(const float* __restrict__ grad, const float* __restric
     gm = wmax[0];
     for (uint32_t w = 1; w < (blockDim.x >> 6); w++) gm = fmaxf(gm, wmax[w]);
     if (!(gm > 0.0f) || !(gm < INFINITY)) {   // nothing to add (or non-finite gradients: leave them to the float path's semantics)
-        if (gm > 0.0f) lz_grid_level_scatter<D, C, false>(grad, inputs, gg, b0, b1, B, L, level, scale_l, res, hs, mode, gridtype, align_corners, sample_major);
+        if (gm > 0.0f) lz_grid_level_scatter<D, C>(grad, inputs, gg, b0, b1, B, L, level, lvl, gridtype, align_corners, sample_major);
         return;
     }
     int ex;
@@ -1044,32 +889,21 @@ lz_k_grid_backward_lds_fx(const float* __restrict__ grad, const float* __restric
         return (unsigned long long)(__double_as_longlong(t) - 0x4338000000000000ll);
     };
     auto scatter_at = [&](const float (&x)[D], const float (&gcur)[C]) {
-        bool oob = false;
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++)
-            if (x[d] < 0 || x[d] > 1) oob = true;
-        if (oob) return;
-        float pos[D];
-        uint32_t pg[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            pos[d] = lz_fmaf(x[d], scale_l, align_corners ? 0.0f : 0.5f);
-            pg[d] = (uint32_t)floorf(pos[d]);
-            pos[d] -= (float)pg[d];
-        }
+        const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+        if (cell.oob) return;
         if constexpr (D == 2) {
-            if (mode != 2u) {
+            if (lvl.mode != 2u) {
                 // the planes of the triplane head: the row term of the two upper corners is the lower one plus a constant (mod 2^32) and the
                 // dense product fits the 24-bit multiplier -- one quarter-rate multiply per sample instead of up to eight; same indices,
                 // same weights (1 * a * b == a * b), same order of the four additions
-                const uint32_t s1 = align_corners ? res : res + 1;
-                const uint32_t r0 = mode == 1u ? pg[1] * 2654435761u : __umul24(pg[1], s1);
+                const uint32_t mode = lvl.mode, s1 = align_corners ? lvl.res : lvl.res + 1;
+                const uint32_t r0 = mode == 1u ? cell.pg[1] * 2654435761u : __umul24(cell.pg[1], s1);
                 const uint32_t r1 = r0 + (mode == 1u ? 2654435761u : s1);
-                const float wx[2] = {1 - pos[0], pos[0]}, wy[2] = {1 - pos[1], pos[1]};
+                const float wx[2] = {1 - cell.pos[0], cell.pos[0]}, wy[2] = {1 - cell.pos[1], cell.pos[1]};
 #pragma unroll
                 for (uint32_t idx = 0; idx < 4; idx++) {
-                    const uint32_t c0 = pg[0] + (idx & 1u), rr = (idx >> 1) ? r1 : r0;
-                    const uint32_t index = (mode == 1u ? ((c0 ^ rr) & (hs - 1u)) : c0 + rr) * C;
+                    const uint32_t c0 = cell.pg[0] + (idx & 1u), rr = (idx >> 1) ? r1 : r0;
+                    const uint32_t index = (mode == 1u ? ((c0 ^ rr) & (lvl.hs - 1u)) : c0 + rr) * C;
                     const float w = wx[idx & 1u] * wy[idx >> 1];
 #pragma unroll
                     for (uint32_t ch = 0; ch < C; ch++) {
@@ -1079,20 +913,12 @@ lz_k_grid_backward_lds_fx(const float* __restrict__ grad, const float* __restric
                 return;
             }
         }
-        uint32_t gterm[D][2];
-        if (mode != 2u) lz_grid_terms<D>(pg, mode, res, align_corners, gterm);
+        uint32_t term[D][2];
+        lz_grid_terms<D>(lvl, cell, align_corners, term);
 #pragma unroll
         for (uint32_t idx = 0; idx < (1u << D); idx++) {
-            float w = 1.0f;
-            uint32_t pl[D];
-#pragma unroll
-            for (uint32_t d = 0; d < D; d++) {
-                if ((idx & (1u << d)) == 0) { w *= 1 - pos[d]; pl[d] = pg[d]; }
-                else { w *= pos[d]; pl[d] = pg[d] + 1; }
-            }
-            uint32_t index;
-            if (mode == 2u) index = lz_grid_index<D>(C, gridtype, align_corners, hs, res, pl);
-            else index = lz_grid_corner<D>(gterm, idx, mode, hs) * C;
+            const float w = lz_grid_weight<D>(cell, idx);
+            const uint32_t index = lz_grid_corner_index<D>(lvl, cell, term, idx, C, gridtype, align_corners);
 #pragma unroll
             for (uint32_t ch = 0; ch < C; ch++) {
                 __hip_atomic_fetch_add(lz_grid_acc64 + index + ch, to_fixed(w * gcur[ch]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1320,8 +1146,7 @@ static void lz_grid_bwd_launch(const T* grad, const float* inputs, const int* of
         }
     }
     if constexpr (sizeof(T) == 4 && C <= 2 && D >= 2) {
-        static const bool plain = getenv("LZ_GRID_BWD_PLAIN") != nullptr;   // diagnostic: the one-lane-per-(sample, level) kernel
-        if (!done && !plain && B >= 4096) {  // big tables: lanes share lines (lz_k_grid_backward_xc)
+        if (!done && B >= 4096) {  // big tables: lanes share lines (lz_k_grid_backward_xc)
             hipLaunchKernelGGL((lz_k_grid_backward_xc<D, C>), dim3(lz_div_up((uint64_t)B * 2 * C, 256), L, 1), block, 0, st, grad, inputs, offsets,
                                gemb, B, L, lv, gridtype, ac, sm);
             done = true;
