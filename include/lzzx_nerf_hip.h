@@ -763,6 +763,17 @@ typedef struct {
 } lz_frame_ngp;
 /* enqueue `n_iterations` iterations (march -> gather -> head -> composite, 4 launches each) back to back; parity as lz_loop_run */
 int lz_ngp_loop_run(const lz_frame_ngp* f, uint32_t parity, uint32_t n_iterations, lz_stream_t stream);
+/* The same network in the reference's autocast arithmetic (half features, every Linear half in / f32 accumulation / half out, sigma =
+ * exp in f32 of the half pre-activation, rgb = half sigmoid) as ONE kernel on v_mfma_f32_32x32x16_f16 (16 MFMAs per 32 samples).
+ * Additive under ABI version 11: new entries only, lz_frame_ngp and every existing entry unchanged.
+ * packed16: LZ_NGP_PACKED_F16_BYTES bytes of half weights (lzzx_nerf_amd/ngp.py: pack_weights_f16); feats: feat_layout 2 (tiled f16,
+ * lz_grid_encode_forward_tiled with emb_f16 = 1) is the only layout; dirs, rows, count, sigmas, rgbs as lz_ngp_head_forward (sigmas /
+ * rgbs are f32 arrays: rgbs hold half values). */
+#define LZ_NGP_PACKED_F16_BYTES 16384
+int lz_ngp_head_forward_f16(const void* packed16, const void* feats, int feat_layout, const float* dirs, uint32_t rows, const int32_t* count,
+                            float* sigmas, float* rgbs, lz_stream_t stream);
+/* lz_ngp_loop_run with lz_ngp_head_forward_f16 as the head (f->packed is not read); requires f->emb_f16 == 1 */
+int lz_ngp_loop_run_f16(const lz_frame_ngp* f, const void* packed16, uint32_t parity, uint32_t n_iterations, lz_stream_t stream);
 
 /* Multi-GPU tile hand-off without a collective (lzzx_nerf_amd/dist.py: PeerTileGatherer): every rank copies its rendered tile straight
  * into each peer's frame buffer (one xGMI hop), then raises its flag there; lz_wait_flags makes `stream` wait, ON THE DEVICE, until all `n`

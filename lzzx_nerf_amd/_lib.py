@@ -119,6 +119,8 @@ SIGNATURES = {
     "lz_grid_encode_forward_tiled": [vp, vp, vp, vp, u32, vp, f32, u32, u32, u32, f32, u32, u32, i32, i32, vp],
     "lz_ngp_head_forward": [vp, vp, i32, vp, u32, vp, vp, vp, vp],
     "lz_ngp_loop_run": [C.POINTER(FrameNgp), u32, u32, vp],
+    "lz_ngp_head_forward_f16": [vp, vp, i32, vp, u32, vp, vp, vp, vp],
+    "lz_ngp_loop_run_f16": [C.POINTER(FrameNgp), vp, u32, u32, vp],
     "lz_timing_create": [u32, C.POINTER(vp)],
     "lz_timing_destroy": [vp],
     "lz_timing_reset": [vp],

@@ -21,6 +21,7 @@
 #include "lzzx_detmath.h"
 #include "lzzx_sh_eval.h"
 #include "lz_head_layers.h"
+#include "lz_head_f16w_slice.h"   // lz_k_ngp_head16: the 32x32x16 f16 operand layout, w_pack / w_zero, h_cvt2 / h_round
 #include <hip/hip_fp16.h>
 
 // fragment (ks, ft) of a layer: 64 floats, lane l = W[16 ft + (l & 15)][k(ks, l >> 4)]
@@ -217,11 +218,150 @@ extern "C" int lz_ngp_head_forward(const float* packed, const void* feats, int f
     return LZ_OK;
 }
 
+// ==================================================================================================================================
+// lz_k_ngp_head16: the same network in the arithmetic the reference renders in by default (`-O` => --fp16: torch.autocast, CUDA policy)
+//   features   half, straight from the f16 tiled gather (grid.py:38-39 gathers from a half copy of the table under autocast)
+//   Linear     half input and weight, f32 accumulation, half output (nn.Linear is on autocast's half list); ReLU on the half value
+//   sigma      exp of the half pre-activation in f32 (exp is on CUDA autocast's fp32 list): lz_expf, so its bits follow from the
+//              pre-activation's
+//   colour in  cat([SH f32, geometry half]) promotes to f32; colour_net.0's cast rounds SH to half (the geometry is already half)
+//   rgb        sigmoid of the half output, rounded to half (sigmoid is not listed: it runs in the input type)
+// tests/ngp_fp16_checker.py restates the sequence; tests/golden/reference_ngp_autocast.npz pins it to the reference's own modules.
+//
+// Shape: 32-sample slices on v_mfma_f32_32x32x16_f16, the layout of lz_head_f16w_slice.h (lane l = (s = l & 31, h = l >> 5), B operand
+// of k-step ks = k slots 16 ks + 8 h + j of sample s, D register i = output row (i & 3) + 8 (i >> 2) + 4 h).  Per 32 samples:
+//   sigma_net.0  32 -> 64   2 k-steps x 2 tiles   B: the gathered halves, k slot = feature (lane half h reads levels 8 ks + 4 h .. + 3)
+//   sigma_net.1  64 -> 16   4 x 1                 B: sigma_net.0's D tiles in registers (w_chain); tile rows 16..31 zero
+//   colour_net.0 32 -> 64   2 x 2                 k-step 0: SH components 8 h + j; k-step 1: sigma_net.1's tile (w_chain), sigma's row 0
+//   colour_net.1 64 -> 3    4 x 1                 B: colour_net.0's D tiles (w_chain)
+// 16 MFMAs where the f32 head issues 192 v_mfma_f32_16x16x4_f32.  The packer (ngp.py: pack_weights_f16) permutes two sets of rows so
+// that the four transcendentals of a sample sit two per lane: sigma_net output 0 (sigma) at tile row 4 and output 4 at row 0; colour
+// channels 0 / 1 / 2 at tile rows 0 / 4 / 1.  Lane half 0 then holds channel 0 (register 0) and channel 2 (register 1), lane half 1
+// channel 1 (register 0) and the sigma pre-activation (sigma_net.1's register 0).
+#define LZN16_S1 0     // fragment bases (fragment (ks, ft) at base + ks * NT + ft; 64 lanes x 8 halves each)
+#define LZN16_S2 4
+#define LZN16_C1 8
+#define LZN16_C2 12
+#define LZN16_FRAGS 16
+static_assert(LZN16_FRAGS * 64 * 16 == LZ_NGP_PACKED_F16_BYTES, "half image size mismatch with the header");
+
+struct LzNgp16K {
+    const lz_h8* packed;
+    const uint32_t* feats;  // tiled f16 features, one half2 (both channels of a level) per word
+    const float* dirs;
+    const int* count;
+    float* sigmas;
+    float* rgbs;
+    uint32_t rows;
+};
+
+template <int KS, int NT>
+__device__ __forceinline__ void lzn16_layer(const lz_h8* __restrict__ frags, int lane, const lz_h8 (&b)[KS], lz_f16v (&acc)[NT]) {
+#pragma unroll
+    for (int ft = 0; ft < NT; ft++) acc[ft] = w_zero();
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++)
+#pragma unroll
+        for (int ft = 0; ft < NT; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(frags[(ks * NT + ft) * 64 + lane], b[ks], acc[ft], 0, 0, 0);
+}
+
+__global__ void __launch_bounds__(LZN_WG) lz_k_ngp_head16(LzNgp16K P) {
+    __shared__ lz_h8 wl[LZN16_FRAGS * 64];
+    for (uint32_t i = threadIdx.x; i < LZN16_FRAGS * 64; i += blockDim.x) wl[i] = P.packed[i];
+    __syncthreads();
+    uint32_t rows = P.rows;
+    if (P.count) {
+        const int c = *P.count;
+        rows = c < 0 ? 0u : ((uint32_t)c < rows ? (uint32_t)c : rows);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & 31, h = lane >> 5;
+    const uint32_t n_slices = (rows + 31u) / 32u, Tn = LZ_GRID_TILE_ROWS;
+    // the inputs of a pass: this lane's eight feature words (levels 8 ks + 4 h + i, i < 4, of sample s) and the direction
+    struct In { uint32_t row; bool valid; uint32_t f[8]; float dx, dy, dz; };
+    auto load = [&](uint32_t slice, In& I) {
+        I.row = slice * 32u + (uint32_t)s;
+        I.valid = I.row < rows;
+        const uint32_t r = I.valid ? I.row : rows - 1u;
+        const uint32_t tile = r / Tn, t = r - tile * Tn, b0 = tile * Tn, n = (P.rows - b0 < Tn) ? P.rows - b0 : Tn;
+        const uint32_t* f = P.feats + (size_t)b0 * 16;
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) I.f[4 * ks + i] = f[(size_t)(8 * ks + 4 * h + i) * n + t];
+        I.dx = P.dirs[(size_t)r * 3]; I.dy = P.dirs[(size_t)r * 3 + 1]; I.dz = P.dirs[(size_t)r * 3 + 2];
+    };
+    const uint32_t stride = gridDim.x * (LZN_WG / 64u);
+    uint32_t slice = blockIdx.x * (LZN_WG / 64u) + (uint32_t)wave;
+    if (rows == 0 || slice >= n_slices) return;
+    In nxt;
+    load(slice, nxt);
+    for (; slice < n_slices; slice += stride) {
+        const In cur = nxt;     // the next pass's loads are in flight under this pass's 16 MFMAs
+        if (slice + stride < n_slices) load(slice + stride, nxt);
+        // ---------------- sigma_net: 32 -> 64 (ReLU) -> 16 ----------------
+        lz_h8 b1[2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+            const lz_u4v w = {cur.f[4 * ks], cur.f[4 * ks + 1], cur.f[4 * ks + 2], cur.f[4 * ks + 3]};
+            b1[ks] = __builtin_bit_cast(lz_h8, w);
+        }
+        lz_f16v s1[2];
+        lzn16_layer<2, 2>(wl + LZN16_S1 * 64, lane, b1, s1);
+        const lz_h8 b2[4] = {w_pack(s1[0], 0, true), w_pack(s1[0], 1, true), w_pack(s1[1], 0, true), w_pack(s1[1], 1, true)};
+        lz_f16v s2[1];
+        lzn16_layer<4, 1>(wl + LZN16_S2 * 64, lane, b2, s2);
+        // ---------------- colour_net: [SH(4) | sigma_net's 16 outputs, sigma's weighted 0] -> 64 (ReLU) -> 3 ----------------
+        lz_h8 c1in[2];
+        {
+            float sh[16];
+            lz_sh_eval(cur.dx, cur.dy, cur.dz, 4, sh, nullptr, nullptr, nullptr);
+            const lz_u4v w = {h_cvt2(h ? sh[8] : sh[0], h ? sh[9] : sh[1], false), h_cvt2(h ? sh[10] : sh[2], h ? sh[11] : sh[3], false),
+                              h_cvt2(h ? sh[12] : sh[4], h ? sh[13] : sh[5], false), h_cvt2(h ? sh[14] : sh[6], h ? sh[15] : sh[7], false)};
+            c1in[0] = __builtin_bit_cast(lz_h8, w);
+        }
+        c1in[1] = w_pack(s2[0], 0, false);
+        lz_f16v c1[2];
+        lzn16_layer<2, 2>(wl + LZN16_C1 * 64, lane, c1in, c1);
+        const lz_h8 c2in[4] = {w_pack(c1[0], 0, true), w_pack(c1[0], 1, true), w_pack(c1[1], 0, true), w_pack(c1[1], 1, true)};
+        lz_f16v c2[1];
+        lzn16_layer<4, 1>(wl + LZN16_C2 * 64, lane, c2in, c2);
+        // ---------------- two transcendentals per lane, one instruction sequence each ----------------
+        // chain A: colour channel h (register 0).  chain B: channel 2 (register 1) on h = 0, sigma on h = 1.  sigmoid(x) = 1 / (1 + exp(-x))
+        // is lz_sigmoidf's own sequence, so both chains are lz_expf / lz_sigmoidf bit for bit.
+        const float pa = (float)h_round(c2[0][0]);
+        const float pb = h ? (float)h_round(s2[0][0]) : (float)h_round(c2[0][1]);
+        const float ea = lz_expf(-pa), eb = lz_expf(h ? pb : -pb);
+        const float rgb_a = (float)h_round(1.0f / (1.0f + ea)), b_out = h ? eb : (float)h_round(1.0f / (1.0f + eb));
+        if (cur.valid) {
+            float* rgb = P.rgbs + (size_t)cur.row * 3;
+            rgb[h] = rgb_a;
+            if (h) P.sigmas[cur.row] = b_out;
+            else rgb[2] = b_out;
+        }
+    }
+}
+
+extern "C" int lz_ngp_head_forward_f16(const void* packed16, const void* feats, int feat_layout, const float* dirs, uint32_t rows, const int32_t* count,
+                                       float* sigmas, float* rgbs, lz_stream_t stream) {
+    if (rows == 0) return LZ_OK;
+    LZ_REQUIRE(packed16 && feats && dirs && sigmas && rgbs, LZ_ERR_BAD_ARGUMENT, "ngp_head_forward_f16: null tensor");
+    LZ_REQUIRE(feat_layout == 2, LZ_ERR_BAD_ARGUMENT, "ngp_head_forward_f16: feat_layout must be 2 (tiled f16)");
+    LzNgp16K K{reinterpret_cast<const lz_h8*>(packed16), reinterpret_cast<const uint32_t*>(feats), dirs, count, sigmas, rgbs, rows};
+    uint32_t passes = LZN_PASSES;
+    while (passes > 1 && lz_div_up(rows, 32 * (LZN_WG / 64) * passes) < 512) passes >>= 1;
+    uint32_t grid = lz_div_up(rows, 32 * (LZN_WG / 64) * passes);
+    const uint32_t cap = (uint32_t)lz_cu_count() * LZN_WG_PER_CU;
+    grid = grid < 1 ? 1 : (grid > cap ? cap : grid);
+    hipLaunchKernelGGL(lz_k_ngp_head16, dim3(grid), dim3(LZN_WG), 0, lz_st(stream), K);
+    LZ_CHECK_LAUNCH("ngp_head_forward_f16");
+    return LZ_OK;
+}
+
 // enqueue `n_iterations` iterations of the reference's inference loop (renderer.py:503-548) around the hash-grid NeRF: march -> gather ->
-// head -> composite, four launches each, no host round trip; iterations past the end of the frame are no-ops on the device
-extern "C" int lz_ngp_loop_run(const lz_frame_ngp* f, uint32_t parity, uint32_t n_iterations, lz_stream_t stream) {
-    LZ_REQUIRE(f, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run: null");
-    LZ_REQUIRE(f->state && f->workspace && f->packed && f->embeddings && f->offsets, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run: incomplete lz_frame_ngp");
+// head -> composite, four launches each, no host round trip; iterations past the end of the frame are no-ops on the device.
+// packed16 == nullptr: the f32 head on f->packed, else the f16 head on packed16 (f->emb_f16 == 1, checked by the caller)
+static int ngp_loop(const lz_frame_ngp* f, const void* packed16, uint32_t parity, uint32_t n_iterations, lz_stream_t stream) {
+    LZ_REQUIRE(f->state && f->workspace && (packed16 || f->packed) && f->embeddings && f->offsets, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run: incomplete lz_frame_ngp");
     if (f->N == 0) return LZ_OK;                 // no ray: nothing to enqueue
     LZ_REQUIRE(f->rays_alive[0] && f->rays_alive[1] && f->feats, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run: incomplete lz_frame_ngp");
     uint32_t cur = parity & 1u;
@@ -236,7 +376,8 @@ extern "C" int lz_ngp_loop_run(const lz_frame_ngp* f, uint32_t parity, uint32_t 
         rc = lz_grid_encode_forward_tiled(f->xyzs, f->embeddings, f->offsets, f->feats, rows, count, f->bound, 3, 2, f->enc_L, f->enc_S, f->enc_H, 0,
                                           0, f->emb_f16, stream);
         if (rc != LZ_OK) return rc;
-        rc = lz_ngp_head_forward(f->packed, f->feats, f->emb_f16 ? 2 : 1, f->dirs, rows, count, f->sigmas, f->rgbs, stream);
+        rc = packed16 ? lz_ngp_head_forward_f16(packed16, f->feats, 2, f->dirs, rows, count, f->sigmas, f->rgbs, stream)
+                      : lz_ngp_head_forward(f->packed, f->feats, f->emb_f16 ? 2 : 1, f->dirs, rows, count, f->sigmas, f->rgbs, stream);
         if (rc != LZ_OK) return rc;
         rc = lz_loop_composite_plain(f->state, f->N, f->T_thresh, f->rays_alive[nxt], f->rays_t, f->sigmas, f->rgbs, f->deltas, f->weights_sum,
                                      f->depth, f->image, f->workspace, stream);
@@ -244,4 +385,16 @@ extern "C" int lz_ngp_loop_run(const lz_frame_ngp* f, uint32_t parity, uint32_t 
         cur = nxt;
     }
     return LZ_OK;
+}
+
+extern "C" int lz_ngp_loop_run(const lz_frame_ngp* f, uint32_t parity, uint32_t n_iterations, lz_stream_t stream) {
+    LZ_REQUIRE(f, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run: null");
+    return ngp_loop(f, nullptr, parity, n_iterations, stream);
+}
+
+// the same loop with lz_k_ngp_head16 as its network: half tables and half features (emb_f16 == 1) are part of that arithmetic
+extern "C" int lz_ngp_loop_run_f16(const lz_frame_ngp* f, const void* packed16, uint32_t parity, uint32_t n_iterations, lz_stream_t stream) {
+    LZ_REQUIRE(f && packed16, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run_f16: null");
+    LZ_REQUIRE(f->emb_f16 == 1, LZ_ERR_BAD_ARGUMENT, "ngp_loop_run_f16: the f16 head reads half features (emb_f16 = 1)");
+    return ngp_loop(f, packed16, parity, n_iterations, stream);
 }

@@ -3,7 +3,8 @@ hashgrid defaults (input_dim 3, num_levels 16, level_dim 2, log2_hashmap_size 19
 MLP 31-64-3 (bias-free Linear + ReLU like network.py:73-94; sigma = exp(row 0), rgb = sigmoid) -- as
 
     FusedHashgridNeRF   the per-sample network: level-major gather (tiled output, never untiled) + ONE MFMA kernel for both MLPs, SH and
-                        the activations (csrc/lz_ngp.hip) -- what `GridEncoder -> MLP -> cat -> MLP` does in ~25 launches per iteration
+                        the activations (csrc/lz_ngp.hip) -- what `GridEncoder -> MLP -> cat -> MLP` does in ~25 launches per iteration;
+                        precision="f16": the same in the reference's torch-autocast arithmetic on f16 MFMAs
     HashgridRenderer    the reference's inference loop (renderer.py:495-548) around it: loop state on the device, 4 launches per
                         iteration (march, gather, head, composite) enqueued by one C call per chunk, no host round trip
 
@@ -53,16 +54,83 @@ def _fragment_tables():
 
 _TABLES = None
 
+NGP_FRAGS_F16 = 16      # LZ_NGP_PACKED_F16_BYTES / 1024: fragments of 64 lanes x 8 halves
+SIGMA_ROW = 4           # tile row of sigma_net's output 0 (sigma) in the f16 head; output 4 takes row 0 (csrc/lz_ngp.hip: lz_k_ngp_head16)
+COLOUR_ROWS = (0, 4, 1)  # tile rows of colour channels 0, 1, 2 in the f16 head
 
-def pack_weights(sigma_w0, sigma_w1, color_w0, color_w1):
-    """the four weight matrices (torch Linear layout [out, in]) -> LZ_NGP_FRAGS * 64 floats in MFMA fragment order, on their device"""
-    global _TABLES
-    shapes = [(HIDDEN, 32), (1 + GEO, HIDDEN), (HIDDEN, 16 + GEO), (3, HIDDEN)]
+
+def _fragment_tables_f16():
+    """(layer, row, col, keep) per packed half of lz_k_ngp_head16 (v_mfma_f32_32x32x16_f16, csrc/lz_head_f16w_slice.h's layout):
+    fragment (ks, ft) of a layer, lane l = (r = l & 31, h = l >> 5), element j = W[tile row 32 ft + r][k slot 16 ks + 8 h + j]"""
+    lane = np.arange(64)
+    r, h = lane & 31, lane >> 5
+    chain = lambda ks, j: 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3)     # w_chain: k slot -> feature of the previous layer's D tiles
+    sig_out = np.array([SIGMA_ROW if t == 0 else (0 if t == SIGMA_ROW else t) for t in range(32)])   # tile row -> sigma_net output
+    col_out = np.full(32, -1)
+    col_out[list(COLOUR_ROWS)] = [0, 1, 2]
+    layer, row, col, keep = [], [], [], []
+
+    def add(which, rr, cc, kk):
+        layer.append(np.full(64, which)); row.append(rr); col.append(cc); keep.append(kk)
+
+    one = np.ones(64, bool)
+    for ks in range(2):                     # sigma_net.0 [64, 32]: k slot = feature (lane half h gathers levels 8 ks + 4 h .. + 3)
+        for ft in range(2):
+            for j in range(8):
+                add(0, 32 * ft + r, 16 * ks + 8 * h + j, one)
+    for ks in range(4):                     # sigma_net.1 [16, 64]: one tile, rows 16..31 zero, sigma at tile row SIGMA_ROW
+        for j in range(8):
+            add(1, np.where(r < 16, sig_out[r], 0), chain(ks, j), r < 16)
+    for ks in range(2):                     # colour_net.0 [64, 31]: SH component 8 h + j, then sigma_net's tile (sigma's row weighted 0)
+        for ft in range(2):
+            for j in range(8):
+                if ks == 0:
+                    add(2, 32 * ft + r, 8 * h + j, one)
+                else:
+                    o = sig_out[chain(0, j)]
+                    add(2, 32 * ft + r, np.maximum(16 + o - 1, 0), o >= 1)
+    for ks in range(4):                     # colour_net.1 [3, 64]: channels at tile rows COLOUR_ROWS, every other row zero
+        for j in range(8):
+            add(3, np.maximum(col_out[r], 0), chain(ks, j), col_out[r] >= 0)
+    # element order: fragment, lane, j
+    n = NGP_FRAGS_F16 * 64 * 8
+    out = [np.concatenate(a).reshape(NGP_FRAGS_F16, 8, 64).transpose(0, 2, 1).reshape(n) for a in (layer, row, col, keep)]
+    return out
+
+
+_TABLES16 = None
+
+
+def pack_weights_f16(sigma_w0, sigma_w1, color_w0, color_w1):
+    """the four weight matrices (torch Linear layout [out, in]) -> LZ_NGP_PACKED_F16_BYTES of halves (float16 tensor on their device) in
+    lz_k_ngp_head16's fragment order; each weight rounded to half once, as autocast casts an f32 Linear weight"""
+    global _TABLES16
     ws = [w.detach().float() for w in (sigma_w0, sigma_w1, color_w0, color_w1)]
+    _check_shapes(ws)
+    if _TABLES16 is None:
+        _TABLES16 = _fragment_tables_f16()
+    layer, row, col, keep = _TABLES16
+    dev = ws[0].device
+    out = torch.zeros(NGP_FRAGS_F16 * 64 * 8, dtype=torch.float16, device=dev)
+    for i, w in enumerate(ws):
+        sel = np.nonzero((layer == i) & keep)[0]
+        out[torch.from_numpy(sel).to(dev)] = w[torch.from_numpy(row[sel]).to(dev), torch.from_numpy(col[sel]).to(dev)].half()
+    return out.contiguous()
+
+
+def _check_shapes(ws):
+    shapes = [(HIDDEN, 32), (1 + GEO, HIDDEN), (HIDDEN, 16 + GEO), (3, HIDDEN)]
     for w, sh in zip(ws, shapes):
         if tuple(w.shape) != sh:
             raise RuntimeError("FusedHashgridNeRF supports sigma MLP 32-64-16 and colour MLP 31-64-3 (got a weight of shape %s where %s is expected); "
                                "other architectures run on the operator API (renderer.NetworkRenderer)" % (tuple(w.shape), sh))
+
+
+def pack_weights(sigma_w0, sigma_w1, color_w0, color_w1):
+    """the four weight matrices (torch Linear layout [out, in]) -> LZ_NGP_FRAGS * 64 floats in MFMA fragment order, on their device"""
+    global _TABLES
+    ws = [w.detach().float() for w in (sigma_w0, sigma_w1, color_w0, color_w1)]
+    _check_shapes(ws)
     if _TABLES is None:
         _TABLES = _fragment_tables()
     layer, row, col, keep = _TABLES
@@ -77,14 +145,23 @@ def pack_weights(sigma_w0, sigma_w1, color_w0, color_w1):
 class FusedHashgridNeRF:
     """encoder: a gridencoder.GridEncoder built by get_encoder('hashgrid') (input_dim 3, level_dim 2, gridtype hash, no align_corners);
     sigma_net / color_net: linear.MLP or anything with `.net[i].weight` (two bias-free layers each).  half_tables: gather from an f16
-    copy of the table and hand f16 features to the head (what grid.py:28,38-39 does under autocast with an even level_dim)."""
+    copy of the table and hand f16 features to the (f32) head (what grid.py:28,38-39 does under autocast with an even level_dim).
+    precision "f16": the whole network in the reference's autocast arithmetic -- half tables and the half head (csrc/lz_ngp.hip:
+    lz_k_ngp_head16); sigma / rgb come back as f32 tensors holding half-derived values (rgb: halves, sigma: exp in f32 of a half)."""
 
-    def __init__(self, encoder, sigma_net, color_net, half_tables=False):
+    def __init__(self, encoder, sigma_net, color_net, half_tables=None, precision="f32"):
         if encoder.input_dim != 3 or encoder.level_dim != 2 or encoder.gridtype_id != 0 or encoder.align_corners or encoder.num_levels != 16:
             raise RuntimeError("FusedHashgridNeRF: the encoder must be get_encoder('hashgrid') with input_dim 3, num_levels 16, level_dim 2")
+        if precision not in ("f32", "f16"):
+            raise ValueError("FusedHashgridNeRF: precision is 'f32' or 'f16', not %r" % (precision,))
+        if precision == "f16" and half_tables is not None and not half_tables:
+            raise ValueError("FusedHashgridNeRF: precision 'f16' gathers from half tables (half_tables=False contradicts it)")
         self.encoder = encoder
-        self.half_tables = bool(half_tables)
-        self.packed = pack_weights(sigma_net.net[0].weight, sigma_net.net[1].weight, color_net.net[0].weight, color_net.net[1].weight)
+        self.precision = precision
+        self.half_tables = precision == "f16" or bool(half_tables)
+        ws = (sigma_net.net[0].weight, sigma_net.net[1].weight, color_net.net[0].weight, color_net.net[1].weight)
+        self.packed = pack_weights(*ws)
+        self.packed16 = pack_weights_f16(*ws) if precision == "f16" else None
         emb = encoder.embeddings.detach()
         self.table = emb.half().contiguous() if self.half_tables else emb.float().contiguous()
         self.offsets = encoder.offsets.contiguous()
@@ -98,7 +175,10 @@ class FusedHashgridNeRF:
         feats = torch.empty(M, 32, dtype=self.table.dtype, device=dev)
         sigma, rgb = out if out is not None else (torch.empty(M, device=dev), torch.empty(M, 3, device=dev))
         self.encode_tiled(xyzs, feats, bound)
-        call("lz_ngp_head_forward", ptr(self.packed), ptr(feats), 2 if self.half_tables else 1, ptr(dirs), M, None, ptr(sigma), ptr(rgb), stream())
+        if self.packed16 is not None:
+            call("lz_ngp_head_forward_f16", ptr(self.packed16), ptr(feats), 2, ptr(dirs), M, None, ptr(sigma), ptr(rgb), stream())
+        else:
+            call("lz_ngp_head_forward", ptr(self.packed), ptr(feats), 2 if self.half_tables else 1, ptr(dirs), M, None, ptr(sigma), ptr(rgb), stream())
         return sigma, rgb
 
     def encode_tiled(self, xyzs, feats, bound, count_ptr=None):
@@ -180,7 +260,10 @@ class HashgridRenderer:
         cur, it, pending = 0, 0, []
         while it < limit:
             n = min(self.chunk, limit - it)
-            call("lz_ngp_loop_run", C.byref(f), cur, n, stream())
+            if net.precision == "f16":
+                call("lz_ngp_loop_run_f16", C.byref(f), ptr(net.packed16), cur, n, stream())
+            else:
+                call("lz_ngp_loop_run", C.byref(f), cur, n, stream())
             cur = (cur + n) & 1
             it += n
             k = len(pending)

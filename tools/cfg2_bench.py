@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """BASELINE cfg2 alone (256 x 256 rays, max_steps 128, all-ones occupancy, hash-grid NeRF): the fused path (lzzx_nerf_amd/ngp.py) under a
-few schedules, next to the operator-API device loop.  tools/cfg2_bench.py [f32|f16] [--ref] [--sched B,C ...]"""
+few schedules, next to the operator-API device loop.  tools/cfg2_bench.py [f32|f16|autocast] [--ref] [B,C ...]
+    f32       f32 tables, f32 head
+    f16       half tables, f32 head (half_tables=True: the bench leg cfg2_fused_f16_ms)
+    autocast  half tables, half head (precision="f16": the reference's torch-autocast arithmetic)"""
 import json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,14 +12,15 @@ from lzzx_nerf_amd.ngp import FusedHashgridNeRF, HashgridRenderer
 from lzzx_nerf_amd.synthetic import GenericHashgridNeRF, synthetic_camera
 from lzzx_nerf_amd.utils import frame_rays
 
-half = len(sys.argv) > 1 and sys.argv[1] == "f16"
+mode = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("f32", "f16", "autocast") else "f32"
+half = mode in ("f16", "autocast")
 dev = torch.device("cuda", 0)
 pose, intr = synthetic_camera(256, 256)
 ro, rd = frame_rays(torch.from_numpy(np.ascontiguousarray(pose)).to(dev), intr, 256, 256)
 aabb = torch.tensor([-1, -1, -1, 1, 1, 1], dtype=torch.float32, device=dev)
 bits = torch.full((128 ** 3 // 8,), 255, dtype=torch.uint8, device=dev)
 g = GenericHashgridNeRF(dev, half_tables=half)
-net = FusedHashgridNeRF(g.enc, g.sigma_net, g.color_net, half_tables=half)
+net = FusedHashgridNeRF(g.enc, g.sigma_net, g.color_net, half_tables=half, precision="f16" if mode == "autocast" else "f32")
 
 
 def timed(f, n=10):
@@ -31,7 +35,7 @@ def timed(f, n=10):
 
 
 scheds = [tuple(int(x) for x in a.split(",")) for a in sys.argv[2:] if "," in a] or [(8, 8), (4, 4), (8, 16), (16, 16), (1, 8)]
-out = {}
+out = {"mode": mode}
 for s in scheds:
     r = HashgridRenderer(net, bits, bound=1.0, aabb=aabb, budget_factor=s[0], n_step_cap=s[1])
     ms, o = timed(lambda: r.render(ro, rd, max_steps=128))
