@@ -789,6 +789,49 @@ int lz_final_blend(const float* image, const float* weights_sum, const float* bg
 int lz_final_blend_rgb24(const float* image, const float* weights_sum, const float* bg, float bg_scalar, uint32_t N,
                          float* out, uint8_t* out_rgb24, lz_stream_t stream);
 
+/* ---- Training objective (TrainerUtil.train_step, TrainerUtil.py:233-367; lzzx_nerf_amd/objective.py) ----------------------------
+ * Additive under ABI version 11: new entries only.  Every reduction is a per-workgroup f64 tree whose partials the last workgroup in
+ * combines in index order (integer ticket, no float atomics): same inputs, same bits.  `workspace`: LZ_OBJECTIVE_WS_BYTES of device
+ * memory, ZEROED ONCE when allocated; each launch leaves its ticket at 0 again.  Launches that share a workspace must be ordered (one
+ * stream).  N = 0 / M = 0 launches nothing and writes nothing.  grad_loss: device f32 [1], the upstream gradient of `loss` (1, or a
+ * GradScaler's scale); it enters every gradient by multiplication only. */
+#define LZ_OBJECTIVE_MAX_GROUPS 2048
+#define LZ_OBJECTIVE_WS_BYTES (64 + LZ_OBJECTIVE_MAX_GROUPS * 8 * 8)
+#define LZ_OBJ_UNC 1u          /* opt.unc_loss */
+#define LZ_OBJ_AMB_AUD 2u      /* opt.amb_aud_loss */
+#define LZ_OBJ_AMB_EYE 4u      /* opt.amb_eye_loss (needs LZ_OBJ_AMB_AUD: the reference's term reads the other's lambda and input) */
+/* Head objective over N rays.  P = clamp(image_raw + (1 - weights_sum) bg, 0, 1) -> pred [N,3]; bg_mode 0: bg_scalar, 1: bg [1],
+ * 2: bg [3], 3: bg [N,3].  face_mask [N] u8 (0 / 1).  unc / amb_aud / amb_eye [N], each required only under its flag.  step_factor =
+ * min(global_step / iters, 1); lambda_amb = opt.lambda_amb; max_steps = opt.max_steps.  loss [1]; aux [8]: the six terms of the loss
+ * (mse after the uncertainty weighting, unc_nll, unc_static, entropy, amb_aud, amb_eye, each scaled as it enters the loss) and, under
+ * LZ_OBJ_UNC, max u and sum exp(u - max u) (words 6, 7), which the backward reads.  Two launches (one without LZ_OBJ_UNC). */
+int lz_objective_head_forward(const float* image_raw, const float* weights_sum, const float* bg, uint32_t bg_mode, float bg_scalar,
+                              const float* target, const uint8_t* face_mask, const float* unc, const float* amb_aud, const float* amb_eye,
+                              uint32_t N, uint32_t flags, float step_factor, float lambda_amb, float max_steps, float* pred, float* loss,
+                              float* aux, void* workspace, lz_stream_t stream);
+/* one elementwise launch: g_image_raw [N,3], g_weights_sum [N] (blend and entropy paths), g_unc / g_amb_aud / g_amb_eye [N] (may be NULL
+ * when their flag is off; written as zeros then if given).  Clamp gradients pass where lo <= x <= hi, as torch's clamp backward. */
+int lz_objective_head_backward(const float* grad_loss, const float* image_raw, const float* weights_sum, const float* bg, uint32_t bg_mode,
+                               float bg_scalar, const float* target, const uint8_t* face_mask, const float* unc, const float* amb_aud,
+                               const float* amb_eye, const float* aux, uint32_t N, uint32_t flags, float step_factor, float lambda_amb,
+                               float max_steps, float* g_image_raw, float* g_weights_sum, float* g_unc, float* g_amb_aud, float* g_amb_eye,
+                               lz_stream_t stream);
+/* Torso objective: mean over N rays and 3 channels of (torso_color - target)^2 plus mean over J anchors of (1 - anchor_points[j,3])^2
+ * (anchor_points [J,4]); loss [1], aux [2] (the two terms).  Backward: g_torso_color [N,3], g_anchor_points [J,4] or NULL. */
+int lz_objective_torso_forward(const float* torso_color, const float* target, const float* anchor_points, uint32_t J, uint32_t N,
+                               float* loss, float* aux, void* workspace, lz_stream_t stream);
+int lz_objective_torso_backward(const float* grad_loss, const float* torso_color, const float* target, const float* anchor_points, uint32_t J,
+                                uint32_t N, float* g_torso_color, float* g_anchor_points, lz_stream_t stream);
+/* Jitter regulariser over M samples: loss = scale * sum over the flagged k of mean_m (raw_k - reg_k)^2, scale = step_factor * 1e-5,
+ * k = (unc, amb_aud, amb_eye) in flag-bit order; aux [3] the scaled means (0 where off).  Backward: g_reg_k [M] for the flagged k
+ * (the gradient flows into the jittered forward only). */
+int lz_objective_jitter_forward(const float* raw_unc, const float* raw_aud, const float* raw_eye, const float* reg_unc, const float* reg_aud,
+                                const float* reg_eye, uint32_t M, uint32_t flags, float scale, float* loss, float* aux, void* workspace,
+                                lz_stream_t stream);
+int lz_objective_jitter_backward(const float* grad_loss, const float* raw_unc, const float* raw_aud, const float* raw_eye, const float* reg_unc,
+                                 const float* reg_aud, const float* reg_eye, uint32_t M, uint32_t flags, float scale, float* g_reg_unc,
+                                 float* g_reg_aud, float* g_reg_eye, lz_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

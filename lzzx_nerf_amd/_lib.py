@@ -158,7 +158,16 @@ SIGNATURES = {
     "lz_triplane_head_backward_recorded_dw16": [C.POINTER(HeadParams), vp, vp, u32, vp, vp, vp, vp, vp, C.POINTER(HeadBwdOut), vp, u32, vp, vp, vp, vp, vp,
                                                 vp, vp],
     "lz_triplane_head_grad_w": [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp],
+    # the training objective (csrc/lz_objective.hip, lzzx_nerf_amd/objective.py)
+    "lz_objective_head_forward": [vp, vp, vp, u32, f32, vp, vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, vp],
+    "lz_objective_head_backward": [vp, vp, vp, vp, u32, f32, vp, vp, vp, vp, vp, vp, u32, u32, f32, f32, f32, vp, vp, vp, vp, vp, vp],
+    "lz_objective_torso_forward": [vp, vp, vp, u32, u32, vp, vp, vp, vp],
+    "lz_objective_torso_backward": [vp, vp, vp, vp, u32, u32, vp, vp, vp],
+    "lz_objective_jitter_forward": [vp] * 6 + [u32, u32, f32, vp, vp, vp, vp],
+    "lz_objective_jitter_backward": [vp] * 7 + [u32, u32, f32, vp, vp, vp, vp],
 }
+LZ_OBJECTIVE_WS_BYTES = 64 + 2048 * 8 * 8   # include/lzzx_nerf_hip.h
+LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t)}
