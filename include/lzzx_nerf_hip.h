@@ -349,6 +349,42 @@ int lz_torso_anchor_encode(const float* pose, const float* anchor_points, float*
 int lz_torso_forward(const lz_torso_params* p, const float* bg_coords, uint32_t N, float* alpha, float* color, float* deform,
                      lz_stream_t stream);
 
+/* ---- Torso training (lzzx_nerf_amd/torso_train.py, FusedTorsoTrainNet; csrc/lz_torso_train.hip) ---------------------------------
+ * Additive under ABI version 11.  The forward is lz_torso_forward's arithmetic (same bits for alpha, colour, deform) plus a threshold
+ * read from device memory and the background mix; the backward recomputes the forward per 16-pixel slice and produces every gradient
+ * of forward_torso in one launch plus one combine launch.  MLP weights, enc_anchor and ind_code gradients are reduced without float
+ * atomics (per-workgroup partials summed in a fixed order: repeated calls give the same bits); the table gradient is ACCUMULATED into
+ * g_emb with float atomics (the reference's scatter), so it is repeatable only up to summation order.  Masked-out pixels contribute
+ * nothing.  N = 0 returns LZ_OK before any pointer is looked at. */
+typedef struct {
+    lz_torso_params net;          /* weights, table, frame constants, occupancy grid; net.density_thresh is used when density_thresh is NULL */
+    const float* density_thresh;  /* device [1] or NULL (update_density_grid_torso's threshold stays on the device) */
+    const float* bg;              /* background [N,3] or NULL: bg_scalar */
+    float bg_scalar;
+    uint32_t mix;                 /* 1: the colour output (and its upstream gradient) is c a + bg (1 - a) (renderer.py:621) */
+    uint32_t n_offsets;           /* entries of net.offsets: 17 (16 levels) */
+} lz_torso_train_params;
+typedef struct {
+    float *g_deform_w0, *g_deform_w1, *g_deform_w2;   /* [32, 76 + ind], [32, 32], [2, 32]: written */
+    float *g_torso_w0, *g_torso_w1, *g_torso_w2;      /* [32, 108 + ind], [32, 32], [4, 32]: written */
+    float* g_emb;                                     /* [sO, 2]: ACCUMULATED (zero it first) */
+    float* g_enc_anchor;                              /* [42]: written */
+    float* g_ind_code;                                /* [ind_dim]: written; NULL allowed when ind_dim == 0 */
+} lz_torso_grads;
+/* device bytes of the backward's workspace (per-workgroup partials; no initialisation needed) */
+size_t lz_torso_train_workspace(void);
+/* bg_coords [N,2] -> alpha [N], color [N,3] (mixed when p->mix), deform [N,2] (may be NULL); masked-out pixels: alpha 0, deform 0,
+ * colour 0 (bg when mixed) */
+int lz_torso_train_forward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, float* alpha, float* color, float* deform,
+                           lz_stream_t stream);
+/* upstream gradients g_alpha [N], g_color [N,3] (of the mixed colour when p->mix), g_deform [N,2]; each may be NULL (zero) */
+int lz_torso_train_backward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha, const float* g_color,
+                            const float* g_deform, const lz_torso_grads* grads, void* workspace, lz_stream_t stream);
+/* the counterpart of lz_torso_anchor_encode: g_enc_anchor [42] -> g_anchor_points [J,4] (written) through the pose inverse and the
+ * perspective divide (network.py:179-183).  J must be 3; J = 0 returns LZ_OK. */
+int lz_torso_anchor_encode_backward(const float* pose, const float* anchor_points, const float* g_enc_anchor, uint32_t J,
+                                    float* g_anchor_points, lz_stream_t stream);
+
 /* Audio conditioning front-end: NeRFNetwork.encode_audio (nerf_triplane/network.py:226-240) = AudioNet
  * (network.py:40-70) on each of n_win windows a[n_win, dim_in, 16], then, when use_att, AudioAttNet (network.py:9-37) -> enc_a
  * [dim_aud]; without attention enc_a is [n_win, dim_aud].  Weights are the reference's Conv1d [out, in, 3] / Linear [out, in]

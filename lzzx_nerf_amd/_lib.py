@@ -31,6 +31,17 @@ class TorsoParams(C.Structure):
                 ("torso_shrink", f32), ("S", f32), ("H", u32), ("density_grid", vp), ("G", u32), ("density_thresh", f32)]
 
 
+class TorsoTrainParams(C.Structure):
+    """mirror of lz_torso_train_params (include/lzzx_nerf_hip.h)"""
+    _fields_ = [("net", TorsoParams), ("density_thresh", vp), ("bg", vp), ("bg_scalar", f32), ("mix", u32), ("n_offsets", u32)]
+
+
+class TorsoGrads(C.Structure):
+    """mirror of lz_torso_grads (include/lzzx_nerf_hip.h)"""
+    _fields_ = [("g_deform_w0", vp), ("g_deform_w1", vp), ("g_deform_w2", vp), ("g_torso_w0", vp), ("g_torso_w1", vp), ("g_torso_w2", vp),
+                ("g_emb", vp), ("g_enc_anchor", vp), ("g_ind_code", vp)]
+
+
 class AudioParams(C.Structure):
     """mirror of lz_audio_params (include/lzzx_nerf_hip.h)"""
     _fields_ = [("c_w", vp * 4), ("c_b", vp * 4), ("fc_w", vp * 2), ("fc_b", vp * 2), ("ac_w", vp * 5), ("ac_b", vp * 5),
@@ -137,6 +148,10 @@ SIGNATURES = {
     "lz_head_pack_weights_f16w": [vp] * 9 + [i32, i32, vp, vp],
     "lz_torso_forward": [C.POINTER(TorsoParams), vp, u32, vp, vp, vp, vp],
     "lz_torso_anchor_encode": [vp, vp, vp, vp],
+    # torso training (csrc/lz_torso_train.hip, lzzx_nerf_amd/torso_train.py)
+    "lz_torso_train_forward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, vp],
+    "lz_torso_train_backward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, C.POINTER(TorsoGrads), vp, vp],
+    "lz_torso_anchor_encode_backward": [vp, vp, vp, u32, vp, vp],
     "lz_audio_encode": [C.POINTER(AudioParams), vp, vp, vp, vp],
     "lz_mark_untrained_grid": [vp, u32, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp],
     "lz_density_grid_points": [vp, u32, u32, f32, vp, vp],
@@ -170,7 +185,7 @@ LZ_OBJECTIVE_WS_BYTES = 64 + 2048 * 8 * 8   # include/lzzx_nerf_hip.h
 LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
-         "lz_triplane_head_grad_w_workspace": ([], C.c_size_t)}
+         "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)
