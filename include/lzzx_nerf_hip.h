@@ -400,6 +400,26 @@ typedef struct {
  * wave per output, with a lane-strided summation order); may be NULL for narrower inputs */
 int lz_audio_encode(const lz_audio_params* p, const float* a, float* enc_a, void* workspace, lz_stream_t stream);
 
+/* ---- Audio encoder training (lzzx_nerf_amd/audio_train.py, FusedAudioTrainNet; csrc/lz_audio_train.hip) -------------------------
+ * Additive under ABI version 11.  The forward is lz_audio_encode itself.  The backward of encode_audio (network.py:226-240) with
+ * respect to every parameter of AudioNet (network.py:40-70) and AudioAttNet (network.py:9-37), the gradients the reference's
+ * optimizer receives from get_params (network.py:333, 344): two launches, no float atomics, every sum in a fixed order (the same bits
+ * on every call), every element of every gradient written.  No gradient to the audio features (they are data in train_step). */
+typedef struct {
+    float* g_c_w[4]; float* g_c_b[4];     /* of audio_net.encoder_conv.{0,2,4,6}: [32|64, Cin, 3], [32|64] */
+    float* g_fc_w[2]; float* g_fc_b[2];   /* of audio_net.encoder_fc1.{0,2}: [64, 64], [64], [dim_aud, 64], [dim_aud] */
+    float* g_ac_w[5]; float* g_ac_b[5];   /* of audio_att_net.attentionConvNet.{0,2,4,6,8} (with p->use_att; ignored without) */
+    float* g_al_w; float* g_al_b;         /* of audio_att_net.attentionNet.0: [n_win, n_win], [n_win] (with p->use_att) */
+} lz_audio_grads;
+/* workspace bytes of lz_audio_train_backward: the gradient at encoder_conv.0's pre-activation, [8, 32, 8] floats */
+size_t lz_audio_train_workspace(void);
+/* a [n_win, dim_in, 16]: the windows the forward saw; conv1_out: what lz_audio_encode left in its workspace (n_win * 256 floats, the
+ * first layer's output) when dim_in >= 128, ignored (may be NULL) below; d_enc_a: upstream gradient, [dim_aud] with attention,
+ * [n_win, dim_aud] without; grads: every pointer written.  Limits of lz_audio_encode; attention needs n_win = 8 (AudioAttNet's
+ * seq_len, network.py:10); a workspace of lz_audio_train_workspace() bytes is always required. */
+int lz_audio_train_backward(const lz_audio_params* p, const float* a, const float* conv1_out, const float* d_enc_a, const lz_audio_grads* grads,
+                            void* workspace, lz_stream_t stream);
+
 /* Tall-skinny bias-free Linear for the training path of the heads (the reference's MLP, network.py:73-94, is a stack of
  * nn.Linear(bias=False) with K, N <= 84 over M ~ 1e6..1e7 samples; torch dispatches them to library GEMMs).  Row-major f32,
  * explicit leading dimensions (column slices of wider buffers are fine), v_mfma_f32_16x16x4_f32.

@@ -48,6 +48,12 @@ class AudioParams(C.Structure):
                 ("al_w", vp), ("al_b", vp), ("dim_in", u32), ("dim_aud", u32), ("n_win", u32), ("use_att", u32)]
 
 
+class AudioGrads(C.Structure):
+    """mirror of lz_audio_grads (include/lzzx_nerf_hip.h)"""
+    _fields_ = [("g_c_w", vp * 4), ("g_c_b", vp * 4), ("g_fc_w", vp * 2), ("g_fc_b", vp * 2), ("g_ac_w", vp * 5), ("g_ac_b", vp * 5),
+                ("g_al_w", vp), ("g_al_b", vp)]
+
+
 class Frame(C.Structure):
     """mirror of lz_frame (include/lzzx_nerf_hip.h)"""
     _fields_ = [("head", HeadParams), ("state", vp), ("workspace", vp), ("rays_alive", vp * 2), ("rays_t", vp), ("rays_o", vp),
@@ -153,6 +159,8 @@ SIGNATURES = {
     "lz_torso_train_backward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, C.POINTER(TorsoGrads), vp, vp],
     "lz_torso_anchor_encode_backward": [vp, vp, vp, u32, vp, vp],
     "lz_audio_encode": [C.POINTER(AudioParams), vp, vp, vp, vp],
+    # audio encoder training (csrc/lz_audio_train.hip, lzzx_nerf_amd/audio_train.py)
+    "lz_audio_train_backward": [C.POINTER(AudioParams), vp, vp, vp, C.POINTER(AudioGrads), vp, vp],
     "lz_mark_untrained_grid": [vp, u32, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp],
     "lz_density_grid_points": [vp, u32, u32, f32, vp, vp],
     "lz_density_grid_torso_points": [vp, u32, vp, vp],
@@ -185,7 +193,8 @@ LZ_OBJECTIVE_WS_BYTES = 64 + 2048 * 8 * 8   # include/lzzx_nerf_hip.h
 LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
-         "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t)}
+         "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
+         "lz_audio_train_workspace": ([], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

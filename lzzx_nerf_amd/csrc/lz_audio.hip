@@ -5,52 +5,12 @@
 // MMAC with strictly sequential layers, so it is ONE workgroup: every layer is a loop over its outputs, activations ping-pong
 // between two LDS buffers, weights stream from L2.  Arithmetic = explicit f32 fma chains (input channel outer, tap inner; bias
 // added after the chain), restated by oracle/audio.py.
-#include "lz_common.h"
-#include "lzzx_detmath.h"
-
-#define LZ_AUDIO_THREADS 1024
-#define LZ_AUDIO_BUF 2048   // floats: largest activation is [8, 32, 8]
-
-__device__ __forceinline__ float lz_lrelu(float v) { return v > 0.0f ? v : 0.02f * v; }   // nn.LeakyReLU(0.02)
-
-// y[n][Cout][Lout] = lrelu(conv1d(x[n][Cin][Lin], w[Cout][Cin][3], stride, padding 1) + b)
-__device__ __forceinline__ void lz_conv1d_k3(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                             float* __restrict__ y, uint32_t n, uint32_t Cin, uint32_t Cout, uint32_t Lin, uint32_t stride) {
-    const uint32_t Lout = (Lin - 1) / stride + 1;   // (Lin + 2 - 3) / stride + 1
-    for (uint32_t idx = threadIdx.x; idx < n * Cout * Lout; idx += blockDim.x) {
-        const uint32_t t = idx % Lout, o = (idx / Lout) % Cout, win = idx / (Lout * Cout);
-        const float* xr = x + (size_t)win * Cin * Lin;
-        const float* wr = w + (size_t)o * Cin * 3;
-        float acc = 0.0f;
-        for (uint32_t ci = 0; ci < Cin; ci++)
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int pos = (int)(t * stride) + k - 1;
-                if (pos >= 0 && pos < (int)Lin) acc = lz_fmaf(wr[ci * 3 + k], xr[(size_t)ci * Lin + pos], acc);
-            }
-        y[idx] = lz_lrelu(acc + b[o]);
-    }
-    __syncthreads();
-}
-
-// y[n][N] = act(x[n][K] . w[N][K]^T + b)
-__device__ __forceinline__ void lz_fc(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y,
-                                      uint32_t n, uint32_t K, uint32_t N, bool lrelu) {
-    for (uint32_t idx = threadIdx.x; idx < n * N; idx += blockDim.x) {
-        const uint32_t o = idx % N, r = idx / N;
-        float acc = 0.0f;
-        for (uint32_t k = 0; k < K; k++) acc = lz_fmaf(w[(size_t)o * K + k], x[(size_t)r * K + k], acc);
-        acc += b[o];
-        y[idx] = lrelu ? lz_lrelu(acc) : acc;
-    }
-    __syncthreads();
-}
+#include "lz_audio_net.h"   // lz_conv1d_k3, lz_fc, lz_lrelu, softmax: shared with the training backward (lz_audio_train.hip)
 
 // First AudioNet layer for wide inputs (HuBERT: dim_in = 1024, a 3072-term dot product per output): one WAVE per output, lane l
 // owns input channels l, l + 64, ... (fma chain, channel outer, tap inner), the 64 partial sums are combined by an xor-shuffle
 // tree (32, 16, ..., 1), bias added last.  2048 outputs spread over the whole chip instead of 3072 dependent loads per lane of
 // a single workgroup (0.88 ms -> a few microseconds).  y [n, 32, 8] goes to a small scratch buffer.
-#define LZ_AUDIO_WIDE 128   // dim_in from which the wide first layer is used; part of the arithmetic contract (oracle/audio.py)
 __global__ void __launch_bounds__(256)
 lz_k_audio_conv1_wide(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ y, uint32_t n,
                       uint32_t Cin) {
@@ -92,22 +52,14 @@ lz_k_audio_encode(lz_audio_params P, const float* __restrict__ a, float* __restr
         return;
     }
     // ---- AudioAttNet: y = feat^T [1, dim_aud, n] -> convs over the window axis -> [1, 1, n] -> Linear(n, n) -> softmax -> weighted sum
-    for (uint32_t i = threadIdx.x; i < n * da; i += blockDim.x) A[(i % da) * n + i / da] = feat[i];   // permute(0, 2, 1)
-    __syncthreads();
+    lz_audio_transpose(feat, A, n, da);                               // permute(0, 2, 1)
     lz_conv1d_k3(A, P.ac_w[0], P.ac_b[0], B, 1, da, 16, n, 1);
     lz_conv1d_k3(B, P.ac_w[1], P.ac_b[1], A, 1, 16, 8, n, 1);
     lz_conv1d_k3(A, P.ac_w[2], P.ac_b[2], B, 1, 8, 4, n, 1);
     lz_conv1d_k3(B, P.ac_w[3], P.ac_b[3], A, 1, 4, 2, n, 1);
     lz_conv1d_k3(A, P.ac_w[4], P.ac_b[4], B, 1, 2, 1, n, 1);          // B[0..n)
     lz_fc(B, P.al_w, P.al_b, A, 1, n, n, false);                      // logits A[0..n)
-    if (threadIdx.x == 0) {   // softmax over n <= 8 values: max, exp, sum in index order, divide
-        float m = A[0];
-        for (uint32_t i = 1; i < n; i++) m = lz_fmaxf(m, A[i]);
-        float s = 0.0f;
-        for (uint32_t i = 0; i < n; i++) { B[i] = lz_expf(A[i] - m); s += B[i]; }
-        for (uint32_t i = 0; i < n; i++) B[i] = B[i] / s;
-    }
-    __syncthreads();
+    lz_audio_softmax(A, B, n);                                        // weights B[0..n)
     for (uint32_t c = threadIdx.x; c < da; c += blockDim.x) {         // torch.sum(y * x, dim=1)
         float acc = 0.0f;
         for (uint32_t t = 0; t < n; t++) acc = lz_fmaf(B[t], feat[t * da + c], acc);

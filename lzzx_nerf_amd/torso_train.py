@@ -3,8 +3,8 @@ this repo's operators -- frequency encoder (csrc/lz_encoders.hip, forward + back
 (csrc/lz_grid.hip, forward + scatter-add backward + dy/dx for the deformation path) and the bias-free MLPs on the MFMA Linear kernels
 (csrc/lz_linear.hip).  Same parameters and state-dict keys as the reference (`anchor_points`, `torso_deform_net.*`, `torso_encoder.*`,
 `torso_net.*`), so a checkpoint moves between this module, the reference and the one-launch inference kernel (`torso.FusedTorso`)
-unchanged.  The audio nets (`AudioNet`, `AudioAttNet`) are plain torch Conv1d / Linear modules in the reference and train as they are;
-only their fused INFERENCE kernel (`audio.FusedAudioEncoder`) is forward-only.
+unchanged.  The audio nets (`AudioNet`, `AudioAttNet`) are plain torch Conv1d / Linear modules in the reference; their fused training path
+is `audio_train.FusedAudioTrainNet` (the inference kernel `audio.FusedAudioEncoder` is forward-only).
 
 `FusedTorsoTrainNet` is the same network trained through two kernels (csrc/lz_torso_train.hip): a forward that is the inference
 kernel's arithmetic and a backward that recomputes it, plus `run_torso`, the reference's masked torso query with the background mix."""
