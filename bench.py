@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: 512x512 triplane-head inference render at max_steps = 192 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: setup, W warm-up steps, K timed steps, the outputs (--dump-outputs), the line.  Everything
+else it can measure or check -- the side legs (other schedules, precisions, sizes and configurations, the cfg3 training step, the grid
+encoder roofline, the CPU baseline and the parity against the checker), the shader-clock probe and, for N > 1, the other tiling, the clip
+leg and the checks of the gathered frame -- runs only with --full (about 100 s more on one GPU); --no-* flags turn single parts off again.
 
 N > 1 without WORLD_SIZE in the environment: this process spawns `python -m torch.distributed.run --nproc-per-node N` on itself
 BEFORE touching the GPU and exits with the children's code; under torch.distributed.run it is one rank per GPU over RCCL.
@@ -15,14 +20,14 @@ all-ones occupancy grid (dense: nothing is skipped), triplane tables U(-1,1), ML
 N > 1, `--shard frame` (default; BASELINE cfg4 as north_star states it, STRONG scaling): ONE 512x512 frame per step whose rays are
 sharded over the N ranks in row tiles -- `--tiles interleaved` (default: 8-row stripes dealt round-robin, balances the expensive
 middle of the frame) or `contiguous` (rank g renders rays [g N/G, (g+1) N/G)) --, every rank renders its tile with a full model
-replica and ONE RCCL all-gather per frame makes every rank hold the frame (overlapped with the next frame's march).  The other
-tiling and the round-1 clip mode (`--shard clip`: N consecutive frames of a talking-head clip, rank r renders frame r, weak scaling)
-are timed in the same run and reported as labelled legs.
+replica and ONE RCCL all-gather per frame makes every rank hold the frame (overlapped with the next frame's march).  With --full, the
+other tiling and the round-1 clip mode (`--shard clip`: N consecutive frames of a talking-head clip, rank r renders frame r, weak
+scaling) are timed in the same run and reported as labelled legs.
 
 Iteration schedule: every loop iteration marches n_step = max(min(F * N // n_alive, C), 1) samples per alive ray.  The reference uses
 F = 1, C = 8 (renderer.py:513), i.e. N sample rows per iteration and thin launches while most rays are alive; pixels do not depend on F
 and C (each ray marches the same sample sequence and compositing resumes exactly), so the headline runs F = C = 4 and the
-`reference_schedule` leg times F = 1, C = 8 on the same frame and checks that the image and the sample count are identical.
+`reference_schedule` leg (--full) times F = 1, C = 8 on the same frame and checks that the image and the sample count are identical.
 
 Prints one JSON line on rank 0.  `value` = marched samples (delta != 0) per second over all ranks.
 """
@@ -109,7 +114,10 @@ def parse_args():
                     help="fused mode, rays still alive at max_steps: 'reference' = the reference loop's frame-wide count C_eff = sum of its n_step "
                          "(renderer.py:503-548; ranks of a sharded frame sum a small histogram between the kernel's two phases), "
                          "'per_ray' = stop at ceil(max_steps / S) * S (no exchange; not the reference's pixels on such rays)")
-    ap.add_argument("--no-side-legs", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every side leg, the shader-clock probe and (N > 1) the other tiling, the clip leg and the "
+                         "gathered-frame checks; without it a run times the headline alone")
+    ap.add_argument("--no-side-legs", action="store_true", help="headline only (profiling runs; what a run without --full does anyway)")
     ap.add_argument("--detail", default="", help="where the full result (every side leg) is written; default bench_detail.json (under gpurun_out/ if present)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-sample", action="store_true",
@@ -140,6 +148,8 @@ def parse_args():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_side_legs = True
     if args.no_side_legs:
         args.no_train = args.no_cpu_baseline = args.no_grid_roofline = args.no_fat_schedule = args.no_fp16_leg = True
         args.no_occupancy = args.no_dense192 = args.no_cfg5 = True
@@ -233,7 +243,7 @@ def main():
     frames_per_step = world if (world > 1 and args.shard == "clip") else 1
     rays_per_step = N * frames_per_step if args.shard_of <= 1 else job.n_rays
     value = samples_per_step * args.steps / dt
-    image = out["image"].clone()
+    image = out["image"].clone() if not args.no_side_legs else None    # what the side legs compare their frames with
     probe = (C.c_uint64 * 2)()
     if not args.no_clock_probe and world == 1 and not args.no_side_legs:
         # sustained shader clock under the head's load: 8 back-to-back 2M-row launches, counters of one wave of the last one
@@ -271,13 +281,12 @@ def main():
         allms = [torch.zeros_like(mine_ms) for _ in range(world)]
         torch.distributed.all_gather(allms, mine_ms)
         rank_tile_ms = dict(step=[round(float(t[0]), 4) for t in allms], kernel=[round(float(t[1]), 4) for t in allms])
-    # correctness of the gathered frame on every rank: the assembled tiles equal this rank's own tile where they overlap
     gather_ok = gather_equals_unsharded = verify = None
     if world > 1 and args.shard == "frame":
         job.sf.wait()
         if args.verify_frames > 0:
             # K more frames of the same pose, NO barrier between them: every rank compares every gathered frame, word for word, with the frame
-            # the timed region ended on (whose own check against the unsharded reference loop follows below)
+            # the timed region ended on (whose own check against the unsharded reference loop follows below, with --full)
             want = tiles.clone()
             bad = 0
             for _ in range(args.verify_frames):
@@ -287,6 +296,8 @@ def main():
             vb = torch.tensor([float(bad)], dtype=torch.float64, device=device)
             torch.distributed.all_reduce(vb)
             verify = dict(steps=args.verify_frames, mismatching_frames_over_all_ranks=int(vb.item()), barrier_between_steps=False, via=args.gather_via)
+    if world > 1 and args.shard == "frame" and args.full:
+        # correctness of the gathered frame on every rank: the assembled tiles equal this rank's own tile where they overlap
         frame = job.sf.assemble(tiles)
         mine = frame[job.sf.pixels]
         own = out["image_rgb24"] if args.gather == "rgb24" else out["image"]

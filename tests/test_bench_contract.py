@@ -84,3 +84,18 @@ def test_dump_outputs_stays_within_the_budget_and_repeats(tmp_path, monkeypatch)
     rows = np.load(tmp_path / "a" / "image_rows.npy").astype(np.int64)
     assert np.array_equal(np.load(tmp_path / "a" / "image.npy"), arrays["image"][rows])
     assert np.array_equal(np.load(tmp_path / "a" / "image_rgb24.npy"), arrays["image_rgb24"][rows].astype(np.float32))
+
+
+def test_a_plain_run_times_the_headline_alone(monkeypatch):
+    """bench.py without --full turns every side leg and the clock probe off; --full turns them on, and a --no-* flag still turns one off"""
+    import bench
+    legs = ("no_train", "no_cpu_baseline", "no_grid_roofline", "no_fat_schedule", "no_fp16_leg", "no_occupancy", "no_dense192", "no_cfg5")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert not a.full and a.no_side_legs and all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full"])
+    a = bench.parse_args()
+    assert a.full and not a.no_side_legs and not a.no_clock_probe and not any(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse_args()
+    assert a.no_cpu_baseline and not a.no_train and not a.no_side_legs

@@ -103,12 +103,13 @@ def test_device_built_ellipsoid_bitfield_equals_checker():
 
 @pytest.mark.parametrize("extra", [["--max-steps", "64", "--verify-frames", "3"], ["--max-steps", "16", "--scene", "ellipsoid"]])
 def test_bench_self_spawns_two_ranks_and_prints_the_contract_line(tmp_path, extra):
-    """(second case: the reference's deployed max_steps, where the cap binds -- the two ranks all-reduce the cap histogram between the two
-    phases of every frame, and rank 0's check of the gathered frame against its own tile still holds)"""
+    """--full: the other tiling, the clip leg and the checks of the gathered frame are on the line.  (Second case: the reference's
+    deployed max_steps, where the cap binds -- the two ranks all-reduce the cap histogram between the two phases of every frame, and
+    rank 0's check of the gathered frame against its own tile still holds)"""
     env = dict(os.environ, LZ_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128", "--full"] + extra
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -129,6 +130,24 @@ def test_bench_self_spawns_two_ranks_and_prints_the_contract_line(tmp_path, extr
         assert r["verify_frames"]["steps"] == 3 and r["verify_frames"]["mismatching_frames_over_all_ranks"] == 0
     detail = json.load(open(os.path.join(ROOT, r["detail"])))
     assert detail["value"] == r["value"] and "schedule" in detail["config"]
+
+
+def test_bench_two_ranks_without_full_times_the_headline_alone(tmp_path):
+    """a plain N > 1 run: the headline and every rank's own times, none of the legs or checks --full adds"""
+    env = dict(os.environ, LZ_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--size", "128", "--max-steps", "64",
+           "--detail", str(tmp_path / "plain2.json")]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 2 and r["steps"] == 2 and r["value"] > 0 and r["ms_per_step"] > 0 and "one frame ray-sharded x2" in r["config"]["parallelism"]
+    assert len(r["rank_tile_ms"]["step"]) == 2 and min(r["rank_tile_ms"]["step"]) > 0
+    for k in ("tiles_contiguous", "tiles_interleaved", "clip_weak_scaling", "gathered_frame_ok", "gathered_frame_equals_unsharded_reference_loop"):
+        assert k not in r, k
 
 
 def test_peer_tile_hand_off_two_ranks_on_one_card(tmp_path):

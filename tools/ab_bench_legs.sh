@@ -4,7 +4,7 @@
 V=$PWD/lzzx_nerf_amd/lib/variants/$1.so
 for which in old new old new; do
   if [ $which = old ]; then export LZZX_NERF_HIP_SO=$V; else unset LZZX_NERF_HIP_SO; fi
-  python3 bench.py --no-cpu-baseline --no-clock-probe --steps 20 --warmup 3 2>/dev/null | python3 -c "
+  python3 bench.py --full --no-cpu-baseline --no-clock-probe --steps 20 --warmup 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 legs={'headline':d['ms_per_step']}

@@ -5,10 +5,10 @@ try:
 except Exception as e:
     print('rc', $rc, 'NO JSON', e); print(open('gpurun_out/flag_run.err').read()[-600:])
 "; }
-run --size 256 --steps 5
-run --size 1024 --scene ellipsoid --steps 5 --no-train --no-dense192
-run --precision f16 --steps 5 --no-train
-run --gather rgb24 --steps 5 --no-train --no-dense192 --no-grid-roofline --no-cpu-baseline
-run --budget-factor 1 --n-step-cap 8 --steps 5 --no-train --no-dense192 --no-grid-roofline
-run --train-mlp lz --steps 3 --no-dense192 --no-grid-roofline --no-cpu-baseline --no-fp16-leg --no-occupancy --no-reference-schedule
-run --train-mlp torch --steps 3 --no-dense192 --no-grid-roofline --no-cpu-baseline --no-fp16-leg --no-occupancy --no-reference-schedule
+run --full --size 256 --steps 5
+run --full --size 1024 --scene ellipsoid --steps 5 --no-train --no-dense192
+run --full --precision f16 --steps 5 --no-train
+run --full --gather rgb24 --steps 5 --no-train --no-dense192 --no-grid-roofline --no-cpu-baseline
+run --full --budget-factor 1 --n-step-cap 8 --steps 5 --no-train --no-dense192 --no-grid-roofline
+run --full --train-mlp lz --steps 3 --no-dense192 --no-grid-roofline --no-cpu-baseline --no-fp16-leg --no-occupancy --no-reference-schedule
+run --full --train-mlp torch --steps 3 --no-dense192 --no-grid-roofline --no-cpu-baseline --no-fp16-leg --no-occupancy --no-reference-schedule

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 OUT=$REPO/gpurun_out
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trainlegs -- python3 $REPO/bench.py --no-cpu-baseline --no-grid-roofline --no-fat-schedule --no-fp16-leg --no-occupancy --no-dense192 --no-cfg5 --steps 5 > $OUT/prof_trainlegs_bench.json 2> $OUT/prof_trainlegs.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trainlegs -- python3 $REPO/bench.py --full --no-cpu-baseline --no-grid-roofline --no-fat-schedule --no-fp16-leg --no-occupancy --no-dense192 --no-cfg5 --steps 5 > $OUT/prof_trainlegs_bench.json 2> $OUT/prof_trainlegs.err
 cd $REPO
 find $OUT/prof_trainlegs -name "*kernel_stats.csv" -exec cp {} $OUT/trainlegs_kernel_stats.csv \;
 find $OUT/prof_trainlegs -name "*.db" -delete
