@@ -830,6 +830,24 @@ int lz_ngp_head_forward_f16(const void* packed16, const void* feats, int feat_la
                             float* sigmas, float* rgbs, lz_stream_t stream);
 /* lz_ngp_loop_run with lz_ngp_head_forward_f16 as the head (f->packed is not read); requires f->emb_f16 == 1 */
 int lz_ngp_loop_run_f16(const lz_frame_ngp* f, const void* packed16, uint32_t parity, uint32_t n_iterations, lz_stream_t stream);
+/* ---- Hash-grid NeRF training (lzzx_nerf_amd/ngp_train.py, FusedHashgridTrainNeRF; csrc/lz_ngp_train.hip) ----------------------
+ * Additive under ABI version 11: new entries only.  Replaces the backward of sigma_net / color_net under autograd (network.py:73-94:
+ * Linear, ReLU, cat with the SH features, exp, sigmoid).  The forward is lz_ngp_head_forward on tiled f32 features (feat_layout 1).
+ * lz_ngp_head_backward recomputes that forward per 16-sample slice (same fragments, same k order: the forward's bits) and produces
+ *   d_feats       [L, rows, C] = [16, rows, 2] f32: d loss / d features, grad_layout 0 of lz_grid_encode_backward (whose scatter into
+ *                 the table uses float atomics, like gridencoder.cu:226-313: repeatable only up to summation order); rows at or past
+ *                 *count are not written
+ *   g_sigma_w0 [64, 32], g_sigma_w1 [16, 64], g_color_w0 [64, 31], g_color_w1 [3, 64]: every element WRITTEN, reduced without float
+ *                 atomics (per-workgroup partials in `workspace`, added in workgroup order by a second launch): the same bits on every call
+ * from the upstream gradients g_sigma [rows] and g_rgb [rows, 3] (either may be NULL: zero).  packed: lz_ngp_head_forward's image of
+ * the same weights, which are also passed as torch Linear matrices ([out, in], row-major).  feats: the tiled f32 features the forward
+ * read (lz_grid_encode_forward_tiled, emb_f16 = 0); dirs [rows, 3]; count (device int32, may be NULL) as lz_ngp_head_forward.  workspace:
+ * lz_ngp_train_workspace() bytes, no initialisation.  Two launches; rows = 0 returns LZ_OK and writes nothing. */
+size_t lz_ngp_train_workspace(void);
+int lz_ngp_head_backward(const float* packed, const float* sigma_w0, const float* sigma_w1, const float* color_w0, const float* color_w1,
+                         const float* feats, const float* dirs, uint32_t rows, const int32_t* count, const float* g_sigma, const float* g_rgb,
+                         float* d_feats, float* g_sigma_w0, float* g_sigma_w1, float* g_color_w0, float* g_color_w1, void* workspace,
+                         lz_stream_t stream);
 
 /* Multi-GPU tile hand-off without a collective (lzzx_nerf_amd/dist.py: PeerTileGatherer): every rank copies its rendered tile straight
  * into each peer's frame buffer (one xGMI hop), then raises its flag there; lz_wait_flags makes `stream` wait, ON THE DEVICE, until all `n`

@@ -138,6 +138,8 @@ SIGNATURES = {
     "lz_ngp_loop_run": [C.POINTER(FrameNgp), u32, u32, vp],
     "lz_ngp_head_forward_f16": [vp, vp, i32, vp, u32, vp, vp, vp, vp],
     "lz_ngp_loop_run_f16": [C.POINTER(FrameNgp), vp, u32, u32, vp],
+    # hash-grid NeRF training (csrc/lz_ngp_train.hip, lzzx_nerf_amd/ngp_train.py)
+    "lz_ngp_head_backward": [vp] * 7 + [u32] + [vp] * 10,
     "lz_timing_create": [u32, C.POINTER(vp)],
     "lz_timing_destroy": [vp],
     "lz_timing_reset": [vp],
@@ -194,7 +196,7 @@ LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
-         "lz_audio_train_workspace": ([], C.c_size_t)}
+         "lz_audio_train_workspace": ([], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

@@ -17,19 +17,10 @@
 // Arithmetic: every Linear is an fma chain in MFMA k order (oracle/ngp.py spells the order per layer); the first layer's k order follows
 // the tiled layout (lane q of a sample reads levels q, q + 4, q + 8, q + 12, both channels: one 8-byte load each), the hidden layers
 // consume the previous accumulator tile in place ("chained" order, as lz_head.hip).
-#include "lz_common.h"
-#include "lzzx_detmath.h"
-#include "lzzx_sh_eval.h"
-#include "lz_head_layers.h"
+#include "lz_ngp_chain.h"       // fragment layout, the feature load and the f32 chain of lz_k_ngp_head (shared with lz_ngp_train.hip)
 #include "lz_head_f16w_slice.h"   // lz_k_ngp_head16: the 32x32x16 f16 operand layout, w_pack / w_zero, h_cvt2 / h_round
 #include <hip/hip_fp16.h>
 
-// fragment (ks, ft) of a layer: 64 floats, lane l = W[16 ft + (l & 15)][k(ks, l >> 4)]
-#define LZN_S1 0       // 32 -> 64: 8 k-steps x 4 tiles
-#define LZN_S2 32      // 64 -> 16: 16 x 1
-#define LZN_C1 48      // 32 slots (SH 16 | sigma_net output 16, slot of its row 0 weighted 0) -> 64: 8 x 4
-#define LZN_C2 80      // 64 -> 3 (one tile, rows 3..15 zero): 16 x 1
-static_assert(LZN_C2 + 16 == LZ_NGP_FRAGS, "fragment count mismatch with the header");
 #ifndef LZN_WG_PER_CU
 #define LZN_WG_PER_CU 3u
 #endif
@@ -69,130 +60,26 @@ __global__ void __launch_bounds__(LZN_WG) lz_k_ngp_head(LzNgpK P) {
         rows = c < 0 ? 0u : ((uint32_t)c < rows ? (uint32_t)c : rows);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, s = lane & 15, q = lane >> 4;
-    const uint32_t n_slices = (rows + 15u) / 16u, Tn = LZ_GRID_TILE_ROWS;
-    // T slices per pass: every A fragment is read from LDS once and feeds T MFMAs, and the T accumulation chains interleave (the 16-deep
-    // chains of the two 64 -> N layers are dependent MFMAs otherwise)
+    const uint32_t n_slices = (rows + 15u) / 16u;
     constexpr int T = LZN_T;
-    // the inputs of a pass (features as the B operands of sigma_net.0: levels q, q + 4, q + 8, q + 12 of sample s, both channels; direction)
-    struct In { uint32_t row[T]; bool valid[T]; float b1[T][8], dx[T], dy[T], dz[T]; };
-    auto load = [&](uint32_t slice0, In& I) {
-#pragma unroll
-        for (int u = 0; u < T; u++) {
-            I.row[u] = (slice0 + u) * 16u + (uint32_t)s;
-            I.valid[u] = I.row[u] < rows;
-            const uint32_t r = I.valid[u] ? I.row[u] : rows - 1u;
-            if constexpr (FEAT == 0) {
-                const float2* f = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(P.feats) + (size_t)r * 32);
-#pragma unroll
-                for (int i = 0; i < 4; i++) { const float2 v = f[q + 4 * i]; I.b1[u][2 * i] = v.x; I.b1[u][2 * i + 1] = v.y; }
-            } else {
-                const uint32_t tile = r / Tn, t = r - tile * Tn, b0 = tile * Tn, n = (P.rows - b0 < Tn) ? P.rows - b0 : Tn;
-                if constexpr (FEAT == 1) {
-                    const float2* f = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(P.feats) + (size_t)b0 * 32);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { const float2 v = f[(size_t)(q + 4 * i) * n + t]; I.b1[u][2 * i] = v.x; I.b1[u][2 * i + 1] = v.y; }
-                } else {
-                    const __half2* f = reinterpret_cast<const __half2*>(reinterpret_cast<const __half*>(P.feats) + (size_t)b0 * 32);
-#pragma unroll
-                    for (int i = 0; i < 4; i++) { const float2 v = __half22float2(f[(size_t)(q + 4 * i) * n + t]); I.b1[u][2 * i] = v.x; I.b1[u][2 * i + 1] = v.y; }
-                }
-            }
-            I.dx[u] = P.dirs[(size_t)r * 3]; I.dy[u] = P.dirs[(size_t)r * 3 + 1]; I.dz[u] = P.dirs[(size_t)r * 3 + 2];
-        }
-    };
     const uint32_t stride = gridDim.x * (LZN_WG / 64u) * T;
     uint32_t slice0 = (blockIdx.x * (LZN_WG / 64u) + (uint32_t)wave) * T;
     if (rows == 0 || slice0 >= n_slices) return;
-    In nxt;
-    load(slice0, nxt);
+    LznIn<T> nxt;
+    lzn_load<FEAT, T>(P.feats, P.dirs, P.rows, rows, s, q, slice0, nxt);
     for (; slice0 < n_slices; slice0 += stride) {
         // the next pass's inputs are requested before this pass's 96 MFMAs (a wave's pass otherwise starts with a round trip to the tiles)
-        const In cur = nxt;
-        if (slice0 + stride < n_slices) load(slice0 + stride, nxt);
-        const uint32_t (&row)[T] = cur.row;
-        const bool (&valid)[T] = cur.valid;
-        const float (&b1)[T][8] = cur.b1;
-        const float (&dx)[T] = cur.dx, (&dy)[T] = cur.dy, (&dz)[T] = cur.dz;
-        // ---------------- sigma_net: 32 -> 64 (ReLU) -> 16 ----------------
-        float h1[T][16];
-        {
-            lz_f4 acc[T][4];
-#pragma unroll
-            for (int u = 0; u < T; u++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++) acc[u][ft] = lz_f4{0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < 8; ks++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++) {
-                    const float a = wl[(LZN_S1 + ks * 4 + ft) * 64 + lane];
-#pragma unroll
-                    for (int u = 0; u < T; u++) acc[u][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b1[u][ks], acc[u][ft], 0, 0, 0);
-                }
-#pragma unroll
-            for (int u = 0; u < T; u++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                    for (int rr = 0; rr < 4; rr++) h1[u][4 * ft + rr] = lz_relu(acc[u][ft][rr]);
-        }
-        lz_f4 h[T];          // h[rr] = output 4 q + rr of sigma_net: row 0 -> sigma, rows 1..15 -> geometry features
-#pragma unroll
-        for (int u = 0; u < T; u++) h[u] = lz_f4{0, 0, 0, 0};
-#pragma unroll
-        for (int ks = 0; ks < 16; ks++) {
-            const float a = wl[(LZN_S2 + ks) * 64 + lane];
-#pragma unroll
-            for (int u = 0; u < T; u++) h[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, h1[u][ks], h[u], 0, 0, 0);
-        }
-        // ---------------- colour_net: [SH(4) of the direction | geometry] -> 64 (ReLU) -> 3 ----------------
-        float c1[T][16];
-        {
-            float shq[T][4];     // SH components 4 ks + q of this lane's sample
-#pragma unroll
-            for (int u = 0; u < T; u++) {
-                float sh[16];
-                lz_sh_eval(dx[u], dy[u], dz[u], 4, sh, nullptr, nullptr, nullptr);
-#pragma unroll
-                for (int ks = 0; ks < 4; ks++) shq[u][ks] = q == 0 ? sh[4 * ks] : (q == 1 ? sh[4 * ks + 1] : (q == 2 ? sh[4 * ks + 2] : sh[4 * ks + 3]));
-            }
-            lz_f4 acc[T][4];
-#pragma unroll
-            for (int u = 0; u < T; u++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++) acc[u][ft] = lz_f4{0, 0, 0, 0};
-#pragma unroll
-            for (int ks = 0; ks < 8; ks++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++) {
-                    const float a = wl[(LZN_C1 + ks * 4 + ft) * 64 + lane];
-#pragma unroll
-                    for (int u = 0; u < T; u++)      // SH component 4 ks + q, then sigma_net output 4 q + (ks - 4)
-                        acc[u][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, ks < 4 ? shq[u][ks] : h[u][ks - 4], acc[u][ft], 0, 0, 0);
-                }
-#pragma unroll
-            for (int u = 0; u < T; u++)
-#pragma unroll
-                for (int ft = 0; ft < 4; ft++)
-#pragma unroll
-                    for (int rr = 0; rr < 4; rr++) c1[u][4 * ft + rr] = lz_relu(acc[u][ft][rr]);
-        }
-        lz_f4 c[T];
-#pragma unroll
-        for (int u = 0; u < T; u++) c[u] = lz_f4{0, 0, 0, 0};
-#pragma unroll
-        for (int ks = 0; ks < 16; ks++) {
-            const float a = wl[(LZN_C2 + ks) * 64 + lane];
-#pragma unroll
-            for (int u = 0; u < T; u++) c[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, c1[u][ks], c[u], 0, 0, 0);
-        }
+        const LznIn<T> cur = nxt;
+        if (slice0 + stride < n_slices) lzn_load<FEAT, T>(P.feats, P.dirs, P.rows, rows, s, q, slice0 + stride, nxt);
+        LznOut<T> o;
+        lzn_chain<T>(wl, lane, q, cur, o);
 #pragma unroll
         for (int u = 0; u < T; u++)
-            if (q == 0 && valid[u]) {
-                P.sigmas[row[u]] = lz_expf(h[u][0]);
-                P.rgbs[(size_t)row[u] * 3] = lz_sigmoidf(c[u][0]);
-                P.rgbs[(size_t)row[u] * 3 + 1] = lz_sigmoidf(c[u][1]);
-                P.rgbs[(size_t)row[u] * 3 + 2] = lz_sigmoidf(c[u][2]);
+            if (q == 0 && cur.valid[u]) {
+                P.sigmas[cur.row[u]] = lz_expf(o.h[u][0]);
+                P.rgbs[(size_t)cur.row[u] * 3] = lz_sigmoidf(o.c[u][0]);
+                P.rgbs[(size_t)cur.row[u] * 3 + 1] = lz_sigmoidf(o.c[u][1]);
+                P.rgbs[(size_t)cur.row[u] * 3 + 2] = lz_sigmoidf(o.c[u][2]);
             }
     }
 }

@@ -1,0 +1,159 @@
+"""BASELINE cfg2 for TRAINING: the generic hash-grid NeRF of `synthetic.GenericHashgridNeRF.net` (get_encoder('hashgrid') -> sigma MLP
+32-64-16 -> [SH(4) | 15 geometry features] -> colour MLP 31-64-3, bias-free Linear + ReLU like network.py:73-94, sigma = exp(h[0]),
+rgb = sigmoid) as an autograd Function over fused kernels instead of ~25 operator launches per forward and their mirror images:
+
+    forward   lz_grid_encode_forward_tiled (level-major gather, tiled f32 features) -> lz_ngp_head_forward (csrc/lz_ngp.hip)
+    backward  lz_ngp_head_backward (csrc/lz_ngp_train.hip: recomputes the head, every MLP gradient on the matrix cores, a fixed-order
+              combine of the weight gradients) -> lz_grid_encode_backward (grad_layout 0: the table scatter, float atomics)
+
+Scope: f32 arithmetic and f32 tables at the fixed cfg2 shape; no position / direction gradient.  What is not built is refused with an
+error, never answered with a silently wrong gradient."""
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.autograd import Function
+
+from . import _lib
+from ._util import call, ptr, stream
+from .encoding import get_encoder
+from .linear import MLP
+from .ngp import GEO, HIDDEN, FusedHashgridNeRF, _check_shapes, _fragment_tables
+
+_SHAPES = [(HIDDEN, 32), (1 + GEO, HIDDEN), (HIDDEN, 16 + GEO), (3, HIDDEN)]
+_WS = {}
+_GATHER = {}
+
+
+def _workspace(device):
+    """lz_ngp_train_workspace() bytes per device: per-workgroup partials, rewritten by every backward (no initialisation)"""
+    key = (device.type, device.index)
+    ws = _WS.get(key)
+    if ws is None:
+        ws = _WS[key] = torch.empty(_lib.load().lz_ngp_train_workspace(), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _gather_index(device):
+    """per packed float of lz_ngp_head_forward's image: its index into cat(the four flattened weights, [0]) (ngp.pack_weights' layout).
+    A constant table, copied to the device once from pinned memory without blocking the host"""
+    key = (device.type, device.index)
+    g = _GATHER.get(key)
+    if g is None:
+        layer, row, col, keep = _fragment_tables()
+        sizes = [a * b for a, b in _SHAPES]
+        base = np.cumsum([0] + sizes)
+        ncols = np.array([b for _, b in _SHAPES])
+        idx = np.where(keep, base[layer] + row * ncols[layer] + col, base[-1]).astype(np.int64)
+        host = torch.from_numpy(idx).pin_memory()
+        g = _GATHER[key] = (host, host.to(device, non_blocking=True))
+    return g[1]
+
+
+def _pack(ws):
+    """the four live weight tensors -> LZ_NGP_FRAGS * 64 floats in fragment order (the values ngp.pack_weights writes), on the device"""
+    flat = torch.cat([w.detach().reshape(-1) for w in ws] + [ws[0].new_zeros(1)])
+    return flat[_gather_index(flat.device)]
+
+
+class _NgpTrain(Function):
+    @staticmethod
+    def forward(ctx, meta, xyzs, dirs, emb, ws0, ws1, wc0, wc1):
+        M, dev = xyzs.shape[0], xyzs.device
+        sigma, rgb = torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, 3, dtype=torch.float32, device=dev)
+        packed = _pack((ws0, ws1, wc0, wc1))
+        feats = torch.empty(M, 32, dtype=torch.float32, device=dev)      # tiled: [tile][level][sample in tile][2]
+        if M:
+            call("lz_grid_encode_forward_tiled", ptr(xyzs), ptr(emb), ptr(meta["offsets"]), ptr(feats), M, None, meta["bound"], 3, 2, 16,
+                 meta["S"], meta["H"], 0, 0, 0, stream())
+            call("lz_ngp_head_forward", ptr(packed), ptr(feats), 1, ptr(dirs), M, None, ptr(sigma), ptr(rgb), stream())
+        ctx.meta = meta
+        ctx.save_for_backward(xyzs, dirs, emb, ws0, ws1, wc0, wc1, packed, feats)
+        return sigma, rgb
+
+    @staticmethod
+    def backward(ctx, g_sigma, g_rgb):
+        xyzs, dirs, emb, ws0, ws1, wc0, wc1, packed, feats = ctx.saved_tensors
+        meta = ctx.meta
+        M, dev = xyzs.shape[0], xyzs.device
+        gws = [torch.empty_like(w) for w in (ws0, ws1, wc0, wc1)]
+        g_emb = torch.zeros_like(emb)
+        if M == 0:
+            for g in gws:
+                g.zero_()
+        else:
+            up = lambda t: None if t is None else t.float().contiguous()
+            g_sigma, g_rgb = up(g_sigma), up(g_rgb)
+            d_feats = torch.empty(16, M, 2, dtype=torch.float32, device=dev)
+            call("lz_ngp_head_backward", ptr(packed), ptr(ws0), ptr(ws1), ptr(wc0), ptr(wc1), ptr(feats), ptr(dirs), M, None, ptr(g_sigma),
+                 ptr(g_rgb), ptr(d_feats), *[ptr(g) for g in gws], ptr(_workspace(dev)), stream())
+            # the gather's own mapping, (x + bound) / (2 bound) in f32 (a true division: torch divides by a host scalar as a reciprocal multiply)
+            unit = (xyzs + meta["bound"]) / torch.full((1,), 2.0 * meta["bound"], dtype=torch.float32, device=dev)
+            call("lz_grid_encode_backward", ptr(d_feats), ptr(unit), ptr(emb), ptr(meta["offsets"]), ptr(g_emb), M, 3, 2, 16, meta["S"], meta["H"],
+                 None, None, 0, 0, 0, 0, stream())
+        return (None, None, None, g_emb) + tuple(gws)
+
+
+def _check_encoder(encoder):
+    if (encoder.input_dim != 3 or encoder.level_dim != 2 or encoder.gridtype_id != 0 or encoder.align_corners or encoder.num_levels != 16):
+        raise RuntimeError("FusedHashgridTrainNeRF: the encoder must be get_encoder('hashgrid') with input_dim 3, num_levels 16, level_dim 2 "
+                           "(hash, no align_corners); other encoders train on the operator API")
+
+
+class FusedHashgridTrainNeRF(nn.Module):
+    """The cfg2 network for training as two fused passes (csrc/lz_ngp.hip forward, csrc/lz_ngp_train.hip backward).
+
+    Modules `encoder` (gridencoder.GridEncoder from get_encoder('hashgrid')), `sigma_net` and `color_net` (linear.MLP): the parameters and
+    state-dict keys are theirs (`encoder.embeddings`, `encoder.offsets`, `sigma_net.net.{0,1}.weight`, `color_net.net.{0,1}.weight`), so
+    the modules of a `synthetic.GenericHashgridNeRF` load as they are, or are passed in and shared.  Every call reads the live parameter
+    tensors (writes through `.data`, as an EMA swap-in does, are seen).  forward(xyzs, dirs, bound) gives `ngp.FusedHashgridNeRF`'s bits
+    for sigma and rgb.  The backward returns the table gradient (float atomics: repeatable only up to summation order) and the four weight
+    gradients (a fixed-order reduction: the same bits on every call, exactly linear in the upstream gradient, so GradScaler's powers of
+    two pass through).  No host synchronisation.
+
+    Refused: inputs that require grad (no position / direction gradient), autocast, half tables, other encoder or MLP shapes."""
+
+    def __init__(self, encoder=None, sigma_net=None, color_net=None):
+        super().__init__()
+        if encoder is None:
+            encoder, _ = get_encoder("hashgrid")
+        _check_encoder(encoder)
+        self.encoder = encoder
+        self.sigma_net = sigma_net if sigma_net is not None else MLP(32, 1 + GEO, HIDDEN, 2)
+        self.color_net = color_net if color_net is not None else MLP(16 + GEO, 3, HIDDEN, 2)
+        _check_shapes(self._weights())
+        # GridEncoder hyper-parameters as the kernels take them (gridencoder.h:12: log2 of the per-level scale narrowed to float)
+        self._S = float(np.float32(np.log2(encoder.per_level_scale)))
+        self._H = int(encoder.base_resolution)
+
+    def _weights(self):
+        return (self.sigma_net.net[0].weight, self.sigma_net.net[1].weight, self.color_net.net[0].weight, self.color_net.net[1].weight)
+
+    def forward(self, xyzs, dirs, bound=1.0):
+        """xyzs [..., 3] in [-bound, bound], dirs [..., 3] (unit) -> (sigma [M], rgb [M, 3]), M = the number of points"""
+        if (torch.is_tensor(xyzs) and xyzs.requires_grad) or (torch.is_tensor(dirs) and dirs.requires_grad):
+            raise RuntimeError("FusedHashgridTrainNeRF: no gradient with respect to positions or directions (train_camera); detach them or "
+                               "use the operator path")
+        if torch.is_autocast_enabled("cuda"):
+            raise RuntimeError("FusedHashgridTrainNeRF trains in f32 only: run it outside torch.autocast (f16 training of this network is "
+                               "not built)")
+        emb = self.encoder.embeddings
+        if emb.dtype != torch.float32:
+            raise RuntimeError("FusedHashgridTrainNeRF trains f32 tables only (embeddings are %s)" % emb.dtype)
+        _check_encoder(self.encoder)
+        ws = self._weights()
+        _check_shapes(ws)
+        if any(w.dtype != torch.float32 for w in ws):
+            raise RuntimeError("FusedHashgridTrainNeRF: the MLP weights must be float32")
+        if not emb.is_cuda:
+            raise RuntimeError("FusedHashgridTrainNeRF runs on the GPU: move the module with .cuda()")
+        dev = emb.device
+        xyzs = xyzs.reshape(-1, 3).to(dev, torch.float32).contiguous()
+        dirs = dirs.reshape(-1, 3).to(dev, torch.float32).contiguous()
+        if dirs.shape[0] != xyzs.shape[0]:
+            raise RuntimeError("FusedHashgridTrainNeRF: xyzs and dirs hold different numbers of points")
+        meta = dict(offsets=self.encoder.offsets.to(dev, torch.int32).contiguous(), bound=float(bound), S=self._S, H=self._H)
+        return _NgpTrain.apply(meta, xyzs, dirs, emb.contiguous(), *[w.contiguous() for w in ws])
+
+    def to_inference(self, precision="f32"):
+        """an `ngp.FusedHashgridNeRF` on the current weights (renders through `ngp.HashgridRenderer`); its table is the live parameter"""
+        return FusedHashgridNeRF(self.encoder, self.sigma_net, self.color_net, precision=precision)

@@ -2,6 +2,7 @@
 (/root/reference/nerf_triplane/renderer.py:699-766) without its Python cascade loop, boolean-mask EMA and `.item()` syncs.
 
     mean, thresh = update_density_grid(head, density_grid, density_bitfield, enc_a, eye, bound=1.0)
+    mean, thresh = update_density_grid_ngp(net, density_grid, density_bitfield, bound=1.0)     # the cfg2 hash-grid NeRF
 
 `density_grid` [cascade, G^3] (Morton order, -1 = untrained) and `density_bitfield` [cascade * G^3 / 8] are updated in place,
 exactly as the reference's attributes of the same names; `mean` / `thresh` are 0-d device tensors (the reference's
@@ -41,6 +42,39 @@ def update_density_grid(head, density_grid, density_bitfield, enc_a, eye=None, b
          ptr(density_bitfield), ptr(stats), ptr(workspace), stream())
     # both tensors were written through raw pointers: tell torch (version counters), so that whoever keys derived data on them --
     # TriplaneRenderer.occupied_bounds() on the bitfield -- sees the change
+    torch.autograd.graph.increment_version(density_grid)
+    torch.autograd.graph.increment_version(density_bitfield)
+    return stats[0], stats[1]
+
+
+@torch.no_grad()
+def update_density_grid_ngp(net, density_grid, density_bitfield, bound=1.0, decay=0.95, density_thresh=0.01, density_scale=1.0, noise=None):
+    """The same head branch of `update_extra_state` for the cfg2 hash-grid NeRF: `net` is an `ngp.FusedHashgridNeRF` or an
+    `ngp_train.FusedHashgridTrainNeRF` (its live weights), queried with forward(xyzs, dirs, bound) -> lz_ngp_head_forward.  Points
+    (lz_density_grid_points), EMA, dilation, mean, threshold and bitfield (lz_density_grid_update) as update_density_grid; returns the
+    device scalars (mean, threshold).  No host synchronisation."""
+    cascade, cells = density_grid.shape
+    G = round(cells ** (1 / 3))
+    if G ** 3 != cells or density_grid.dtype != torch.float32 or not density_grid.is_contiguous():
+        raise RuntimeError("density_grid must be a contiguous float32 [cascade, grid_size^3] tensor")
+    if cascade != 1 + math.ceil(math.log2(bound)):
+        raise RuntimeError("cascade does not match bound (renderer.py:93)")
+    dev = density_grid.device
+    n = cascade * cells
+    if noise is None:
+        noise = torch.stack([torch.rand(cells, 3, dtype=torch.float32, device=dev) for _ in range(cascade)])
+    noise = noise.to(dev, torch.float32).contiguous()
+    if noise.numel() != n * 3:
+        raise RuntimeError("noise must hold cascade * grid_size^3 * 3 values")
+    xyzs = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    call("lz_density_grid_points", ptr(noise), cascade, G, float(bound), ptr(xyzs), stream())
+    dirs = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+    dirs[:, 2] = 1.0   # sigma does not depend on the view direction; the head still wants one
+    sigma = net.forward(xyzs, dirs, bound)[0]
+    stats = torch.empty(2, dtype=torch.float32, device=dev)
+    workspace = torch.empty((n + 255) // 256, dtype=torch.float32, device=dev)
+    call("lz_density_grid_update", ptr(sigma), float(density_scale), float(decay), float(density_thresh), cascade, G, ptr(density_grid),
+         ptr(density_bitfield), ptr(stats), ptr(workspace), stream())
     torch.autograd.graph.increment_version(density_grid)
     torch.autograd.graph.increment_version(density_bitfield)
     return stats[0], stats[1]
