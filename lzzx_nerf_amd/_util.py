@@ -30,5 +30,23 @@ def require_cuda(**tensors):
             raise RuntimeError(f"{name} must be a contiguous tensor")
 
 
+_WS = {}
+
+
+def workspace(tag, device, nbytes, zero=False):
+    """a cached byte tensor per (tag, device): kernel scratch that lives across calls (zero: cleared once, when allocated).
+    Launches on it are ordered by the stream; two streams at once would share it (not supported)"""
+    key = (tag, device.type, device.index)
+    ws = _WS.get(key)
+    if ws is None:
+        ws = _WS[key] = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def as_f32(t):
+    """an upstream gradient as the kernels read it: contiguous f32 (None stays None)"""
+    return None if t is None else t.float().contiguous()
+
+
 def call(name, *args):
     _lib.call(name, *args)

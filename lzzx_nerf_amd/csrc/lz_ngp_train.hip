@@ -12,19 +12,18 @@
 // 68 MFMAs, plus the 96 of the recomputed forward.  The table gradient is not formed here: d feats is grad_layout 0 of
 // lz_grid_encode_backward, whose scatter uses float atomics like the reference (gridencoder.cu:226-313).
 //
-// Weight gradients take samples as the MFMA's k dimension (as lz_torso_train.hip): per layer the slice's output gradients and inputs are
-// staged in the wave's LDS as [feature][16 samples] rows, read back four samples per lane as one 16-byte load, and accumulated over the
-// wave's slices into 24 16 x 16 tiles (96 registers).  The four waves' tiles are folded in LDS in wave order, each workgroup writes one
-// partial, and the combine kernel adds the partials in workgroup order: no float atomics, the same bits on every call, and every weight
-// gradient is linear in the upstream gradient (a power-of-two scale passes through exactly).
+// Weight gradients take samples as the MFMA's k dimension (lz_train_wgrad.h, shared with lz_torso_train.hip): per layer the slice's
+// output gradients and inputs are staged in the wave's LDS and accumulated over the wave's slices into 24 16 x 16 tiles (96 registers);
+// the fold and the combine are the header's: no float atomics, the same bits on every call, and every weight gradient is linear in the
+// upstream gradient (a power-of-two scale passes through exactly).
 #include "lz_ngp_chain.h"
+#include "lz_train_wgrad.h"
 
 #ifndef LZNB_WG_PER_CU
 #define LZNB_WG_PER_CU 2u   // 66 KB of LDS per workgroup: two per CU
 #endif
 #define LZNB_WG 256
 #define LZNB_WAVES (LZNB_WG / 64)
-#define LZNB_MAX_GROUPS 512
 // backward fragments, lane l of fragment (ks, ft) = W[k(ks, l >> 4)][16 ft + (l & 15)] (k over the forward layer's outputs)
 #define LZNB_C2 0      // colour_net.1^T: k = channel (l >> 4) < 3; 4 tiles of colour_net.0's outputs
 #define LZNB_C1 4      // colour_net.0^T geometry columns: 16 k-steps (64 outputs, chained) x 1 tile of slots
@@ -50,41 +49,6 @@ struct LzNgpBwdK {
     float* partials;
     uint32_t rows;
 };
-
-// D register rr of tile ft (feature 16 ft + 4 q + rr of sample s) -> staging row
-template <int NT>
-__device__ __forceinline__ void lznb_stage_d(float* __restrict__ rows, int s, int q, const float* v) {
-#pragma unroll
-    for (int ft = 0; ft < NT; ft++)
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) rows[(16 * ft + 4 * q + rr) * 16 + s] = v[4 * ft + rr];
-}
-
-// rows [16 t, 16 t + 16) of a staging block as an MFMA operand with samples as k: lane l -> row 16 t + (l & 15), samples 4 (l >> 4) + 0..3
-__device__ __forceinline__ lz_f4 lznb_rows(const float* __restrict__ rows, int t, int lane) {
-    return *reinterpret_cast<const lz_f4*>(rows + (16 * t + (lane & 15)) * 16 + 4 * (lane >> 4));
-}
-
-template <int FO, int FK>
-__device__ __forceinline__ void lznb_grad_tiles(lz_f4* __restrict__ acc, const float* g_rows, const float* a_rows, int lane) {
-    lz_f4 av[FK];
-#pragma unroll
-    for (int k = 0; k < FK; k++) av[k] = lznb_rows(a_rows, k, lane);
-#pragma unroll
-    for (int o = 0; o < FO; o++) {
-        const lz_f4 gv = lznb_rows(g_rows, o, lane);
-#pragma unroll
-        for (int k = 0; k < FK; k++)
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) acc[o * FK + k] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[ks], av[k][ks], acc[o * FK + k], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void lznb_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ void __launch_bounds__(LZNB_WG, 2) lz_k_ngp_head_backward(LzNgpBwdK P) {
     __shared__ __align__(16) float wl[LZ_NGP_FRAGS * 64];
@@ -152,10 +116,10 @@ __global__ void __launch_bounds__(LZNB_WG, 2) lz_k_ngp_head_backward(LzNgpBwdK P
         }
         // weight gradient of colour_net.1: G = gc (rows 0..3 of region B), inputs c1 (region A)
         stB[q * 16 + s] = gc;
-        lznb_stage_d<4>(stA, s, q, f.c1[0]);
-        lznb_wave_sync();
-        lznb_grad_tiles<1, 4>(gw + 0, stB, stA, lane);
-        lznb_wave_sync();
+        lz_wg_stage_d<4>(stA, s, q, f.c1[0]);
+        lz_wave_lds_sync();
+        lz_wg_tiles<1, 4>(gw + 0, stB, stA, lane);
+        lz_wave_lds_sync();
         // ---- colour_net.0^T (geometry slots) -> sigma_net outputs 1..15; output 0 from sigma ----
         float gh[4];
         {
@@ -167,14 +131,14 @@ __global__ void __launch_bounds__(LZNB_WG, 2) lz_k_ngp_head_backward(LzNgpBwdK P
             if (q == 0) gh[0] = gh0;
         }
         // weight gradient of colour_net.0: G = gc1 (region A), inputs [SH 16 | sigma_net outputs 16] (region B)
-        lznb_stage_d<4>(stA, s, q, gc1);
+        lz_wg_stage_d<4>(stA, s, q, gc1);
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) stB[(4 * ks + q) * 16 + s] = f.shq[0][ks];
 #pragma unroll
         for (int rr = 0; rr < 4; rr++) stB[(16 + 4 * q + rr) * 16 + s] = f.h[0][rr];
-        lznb_wave_sync();
-        lznb_grad_tiles<4, 2>(gw + 4, stA, stB, lane);
-        lznb_wave_sync();
+        lz_wave_lds_sync();
+        lz_wg_tiles<4, 2>(gw + 4, stA, stB, lane);
+        lz_wave_lds_sync();
         // ---- sigma_net.1^T -> ReLU mask ----
         float gh1[16];
         {
@@ -191,11 +155,11 @@ __global__ void __launch_bounds__(LZNB_WG, 2) lz_k_ngp_head_backward(LzNgpBwdK P
                 for (int rr = 0; rr < 4; rr++) gh1[4 * ft + rr] = f.h1[0][4 * ft + rr] > 0.0f ? acc[ft][rr] : 0.0f;
         }
         // weight gradient of sigma_net.1: G = gh (rows 0..15 of region B), inputs h1 (region A)
-        lznb_stage_d<1>(stB, s, q, gh);
-        lznb_stage_d<4>(stA, s, q, f.h1[0]);
-        lznb_wave_sync();
-        lznb_grad_tiles<1, 4>(gw + 12, stB, stA, lane);
-        lznb_wave_sync();
+        lz_wg_stage_d<1>(stB, s, q, gh);
+        lz_wg_stage_d<4>(stA, s, q, f.h1[0]);
+        lz_wave_lds_sync();
+        lz_wg_tiles<1, 4>(gw + 12, stB, stA, lane);
+        lz_wave_lds_sync();
         // ---- sigma_net.0^T -> d feats: feature 16 ft + 4 q + rr = level 8 ft + 2 q + (rr >> 1), channel rr & 1 ----
         {
             lz_f4 acc[2] = {lz_f4{0, 0, 0, 0}, lz_f4{0, 0, 0, 0}};
@@ -214,52 +178,28 @@ __global__ void __launch_bounds__(LZNB_WG, 2) lz_k_ngp_head_backward(LzNgpBwdK P
             }
         }
         // weight gradient of sigma_net.0: G = gh1 (region A), inputs the features (region B; b1[ks] = feature 2 (q + 4 (ks >> 1)) + (ks & 1))
-        lznb_stage_d<4>(stA, s, q, gh1);
+        lz_wg_stage_d<4>(stA, s, q, gh1);
 #pragma unroll
         for (int ks = 0; ks < 8; ks++) stB[(2 * (q + 4 * (ks >> 1)) + (ks & 1)) * 16 + s] = in.b1[0][ks];
-        lznb_wave_sync();
-        lznb_grad_tiles<4, 2>(gw + 16, stA, stB, lane);
-        lznb_wave_sync();
+        lz_wave_lds_sync();
+        lz_wg_tiles<4, 2>(gw + 16, stA, stB, lane);
+        lz_wave_lds_sync();
     }
-    // ---- the workgroup's waves folded in wave order into the staging rows, then one partial per workgroup ----
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < LZNB_WAVES; w++) {
-        if (wave == w) {
-#pragma unroll
-            for (int t = 0; t < LZNB_TILES; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    float* p = stage + t * 256 + r * 64 + lane;
-                    *p = w == 0 ? gw[t][r] : *p + gw[t][r];
-                }
-        }
-        __syncthreads();
-    }
-    float* out = P.partials + (size_t)blockIdx.x * LZNB_ELEMS;
-    for (uint32_t i = threadIdx.x; i < LZNB_ELEMS / 4; i += LZNB_WG)
-        reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(stage)[i];
+    // ---- the waves folded in wave order into the staging rows, then one partial per workgroup ----
+    lz_wg_fold_and_store<LZNB_TILES, LZNB_WAVES>(gw, stage, P.partials + (size_t)blockIdx.x * LZNB_ELEMS, lane, wave);
 }
 
-// ---- combine: the workgroup partials in workgroup order -> the four weight gradients --------------------------------------------------
-// 64 tile elements per block, four threads per element over interleaved quarters of the partials, the quarters added in order.  Tile
-// element (t, register r, lane l) = D[4 (l >> 4) + r][l & 15] of tile t.
+// ---- combine: the workgroup partials in workgroup order (lz_wg_combine) -> the four weight gradients --------------------------------
 struct LzNgpGradOut {
     float *gs0, *gs1, *gc0, *gc1;
 };
 
 __global__ void __launch_bounds__(256) lz_k_ngp_head_grad_combine(const float* __restrict__ partials, uint32_t n_groups, LzNgpGradOut G) {
     __shared__ float red[4][64];
-    const int slot = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + slot;
-    float v = 0.0f;
-    for (uint32_t g = part; g < n_groups; g += 4) v += partials[(size_t)g * LZNB_ELEMS + e];
-    red[part][slot] = v;
-    __syncthreads();
-    if (part != 0) return;
-    v = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
-    const int t = e >> 8, r = (e >> 6) & 3, l = e & 63;
-    const int row = 4 * (l >> 4) + r, col = l & 15;
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+    const float v = lz_wg_combine<LZNB_ELEMS>(partials, n_groups, e, red);
+    if (threadIdx.x >= 64) return;
+    const auto [t, row, col] = lz_wg_elem(e);
     if (t < 4) {                // colour_net.1 [3, 64]
         if (row < 3) G.gc1[row * 64 + 16 * t + col] = v;
     } else if (t < 12) {        // colour_net.0 [64, 31]: input k < 16 = SH column k; k = 16 + j = sigma_net output j -> column 15 + j (j >= 1)
@@ -273,7 +213,7 @@ __global__ void __launch_bounds__(256) lz_k_ngp_head_grad_combine(const float* _
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
-extern "C" size_t lz_ngp_train_workspace(void) { return (size_t)LZNB_MAX_GROUPS * LZNB_ELEMS * sizeof(float); }
+extern "C" size_t lz_ngp_train_workspace(void) { return lz_wg_workspace_bytes(LZNB_TILES); }
 
 extern "C" int lz_ngp_head_backward(const float* packed, const float* sigma_w0, const float* sigma_w1, const float* color_w0, const float* color_w1,
                                     const float* feats, const float* dirs, uint32_t rows, const int32_t* count, const float* g_sigma, const float* g_rgb,
@@ -285,10 +225,7 @@ extern "C" int lz_ngp_head_backward(const float* packed, const float* sigma_w0, 
     LzNgpBwdK K{packed, sigma_w0, sigma_w1, color_w0, color_w1, feats, dirs, count, g_sigma, g_rgb, d_feats, static_cast<float*>(workspace), rows};
     // as lz_ngp_head_forward: as many workgroups as the chip holds at a time (each stages 42 KB of fragments once), each looping over its
     // share of the slices, fewer when there are not four slices per wave
-    uint32_t grid = lz_div_up(rows, 16 * LZNB_WAVES * 4);
-    uint32_t cap = (uint32_t)lz_cu_count() * LZNB_WG_PER_CU;
-    if (cap > LZNB_MAX_GROUPS) cap = LZNB_MAX_GROUPS;
-    grid = grid < 1 ? 1 : (grid > cap ? cap : grid);
+    const uint32_t grid = lz_wg_grid(rows, LZNB_WAVES, LZNB_WG_PER_CU);
     hipStream_t st = lz_st(stream);
     hipLaunchKernelGGL(lz_k_ngp_head_backward, dim3(grid), dim3(LZNB_WG), 0, st, K);
     LZ_CHECK_LAUNCH("ngp_head_backward");

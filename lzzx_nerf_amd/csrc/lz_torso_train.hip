@@ -13,9 +13,10 @@
 // back four pixels per lane as one 16-byte load, and accumulated over the wave's slices into 28 16 x 16 tiles (112 registers).
 // Pixel row 34 of the staged frequency features is set to 1, so the tiles' column 34 carries the pixel sums of the first layers'
 // output gradients: the gradients of the frame-constant inputs (anchor encoding, individual code) and of their weight columns are
-// formed from those sums by the combine kernel.  The four waves' tiles are summed in LDS in wave order, each workgroup writes one
-// partial, and the combine kernel adds the partials in workgroup order: no float atomics, same bits on every call.
+// formed from those sums by the combine kernel.  The staging, the wave fold and the fixed-order combine are lz_train_wgrad.h's: no
+// float atomics, same bits on every call.
 #include "lz_torso_net.h"
+#include "lz_train_wgrad.h"
 
 // backward (transposed) fragments: lane l of fragment (ks, ft) = W[4 ks + (l >> 4)][16 ft + (l & 15)]
 enum { LZTB_T2 = 0, LZTB_T1, LZTB_T0G, LZTB_D2, LZTB_D1, LZTB_LAYERS };
@@ -46,8 +47,7 @@ enum : int {
 //   0-5 D0 (2 x 3, inputs ex)  6-9 D1 (2 x 2)  10-11 D2 (1 x 2)  12-21 T0 (2 x 5, inputs [grid 32 | ex 36])  22-25 T1  26-27 T2
 #define LZTG_TILES 28
 #define LZTG_ELEMS (LZTG_TILES * 256)
-#define LZT_TRAIN_MAX_GROUPS 512
-#define LZTS_SIZE (3 * LZTG_ELEMS > 4 * LZTS_WAVE ? 3 * LZTG_ELEMS : 4 * LZTS_WAVE)   // staging rows, reused by the wave reduction
+#define LZTS_SIZE (LZTG_ELEMS > 4 * LZTS_WAVE ? LZTG_ELEMS : 4 * LZTS_WAVE)   // staging rows, reused by the wave fold
 
 struct LzTorsoTrainArgs {
     LzTorsoArgs a;
@@ -120,34 +120,6 @@ __device__ __forceinline__ void lztb_to_b(lzt_f4 (&acc)[2], const float (&relu_o
         lzt_transpose(acc[t]);
 #pragma unroll
         for (int j = 0; j < 4; j++) g[4 * t + j] = relu_out[4 * t + j] > 0.0f ? acc[t][j] : 0.0f;
-    }
-}
-
-// B-layout registers (register i = feature 4 i + q of pixel s) -> staging rows
-template <int NREG>
-__device__ __forceinline__ void lzt_stage(float* __restrict__ rows, int lane, const float (&v)[NREG]) {
-#pragma unroll
-    for (int i = 0; i < NREG; i++) rows[i * 64 + lane] = v[i];   // row 4 i + q, column s: (4 i + q) * 16 + s
-}
-
-// rows [16 t, 16 t + 16) of a staging block as an MFMA operand with pixels as k: lane l -> row 16 t + (l & 15), pixels 4 (l >> 4) + 0..3
-__device__ __forceinline__ lzt_f4 lzt_rows(const float* __restrict__ rows, int t, int n_rows, int lane) {
-    const int row = 16 * t + (lane & 15);
-    return row < n_rows ? *reinterpret_cast<const lzt_f4*>(rows + row * 16 + 4 * (lane >> 4)) : lzt_f4{0, 0, 0, 0};
-}
-
-template <int FO, int FK, int OSTRIDE = FK>
-__device__ __forceinline__ void lzt_grad_tiles(lzt_f4* __restrict__ acc, const float* g_rows, int g_n, const float* a_rows, int a_n, int lane) {
-    lzt_f4 av[FK];
-#pragma unroll
-    for (int k = 0; k < FK; k++) av[k] = lzt_rows(a_rows, k, a_n, lane);
-#pragma unroll
-    for (int o = 0; o < FO; o++) {
-        const lzt_f4 gv = lzt_rows(g_rows, o, g_n, lane);
-#pragma unroll
-        for (int k = 0; k < FK; k++)
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) acc[o * OSTRIDE + k] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[ks], av[k][ks], acc[o * OSTRIDE + k], 0, 0, 0);
     }
 }
 
@@ -289,53 +261,30 @@ lz_k_torso_train_backward(LzTorsoTrainArgs T, const float* __restrict__ bg_coord
 #pragma unroll
         for (int i = 0; i < 9; i++) ex[i] = f.ex[i];
         if (q == 2) ex[8] = 1.0f;   // row 34: the pixel sums of the first layers' output gradients
-        lzt_stage<9>(st + LZTS_EX, lane, ex);
-        lzt_stage<8>(st + LZTS_RD1, lane, f.bd1);
-        lzt_stage<8>(st + LZTS_RD2, lane, f.bd2);
-        lzt_stage<8>(st + LZTS_GX, lane, f.gx);
-        lzt_stage<8>(st + LZTS_RT1, lane, f.bt1);
-        lzt_stage<8>(st + LZTS_RT2, lane, f.bt2);
-        lzt_stage<8>(st + LZTS_GZ0, lane, gz0);
-        lzt_stage<8>(st + LZTS_GZ1, lane, gz1);
-        lzt_stage<1>(st + LZTS_GDX, lane, gdb);
-        lzt_stage<8>(st + LZTS_GT0, lane, gt0);
-        lzt_stage<8>(st + LZTS_GT1, lane, gt1);
-        lzt_stage<1>(st + LZTS_GO, lane, go);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        lzt_grad_tiles<2, 3>(gw + 0, st + LZTS_GZ0, 32, st + LZTS_EX, 36, lane);
-        lzt_grad_tiles<2, 2>(gw + 6, st + LZTS_GZ1, 32, st + LZTS_RD1, 32, lane);
-        lzt_grad_tiles<1, 2>(gw + 10, st + LZTS_GDX, 4, st + LZTS_RD2, 32, lane);
-        lzt_grad_tiles<2, 2, 5>(gw + 12, st + LZTS_GT0, 32, st + LZTS_GX, 32, lane);   // T0 (2 x 5): grid columns
-        lzt_grad_tiles<2, 3, 5>(gw + 14, st + LZTS_GT0, 32, st + LZTS_EX, 36, lane);   //            frequency columns
-        lzt_grad_tiles<2, 2>(gw + 22, st + LZTS_GT1, 32, st + LZTS_RT1, 32, lane);
-        lzt_grad_tiles<1, 2>(gw + 26, st + LZTS_GO, 4, st + LZTS_RT2, 32, lane);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the next slice overwrites the rows just read
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        lz_wg_stage_b<9>(st + LZTS_EX, lane, ex);
+        lz_wg_stage_b<8>(st + LZTS_RD1, lane, f.bd1);
+        lz_wg_stage_b<8>(st + LZTS_RD2, lane, f.bd2);
+        lz_wg_stage_b<8>(st + LZTS_GX, lane, f.gx);
+        lz_wg_stage_b<8>(st + LZTS_RT1, lane, f.bt1);
+        lz_wg_stage_b<8>(st + LZTS_RT2, lane, f.bt2);
+        lz_wg_stage_b<8>(st + LZTS_GZ0, lane, gz0);
+        lz_wg_stage_b<8>(st + LZTS_GZ1, lane, gz1);
+        lz_wg_stage_b<1>(st + LZTS_GDX, lane, gdb);
+        lz_wg_stage_b<8>(st + LZTS_GT0, lane, gt0);
+        lz_wg_stage_b<8>(st + LZTS_GT1, lane, gt1);
+        lz_wg_stage_b<1>(st + LZTS_GO, lane, go);
+        lz_wave_lds_sync();
+        lz_wg_tiles<2, 3>(gw + 0, st + LZTS_GZ0, 32, st + LZTS_EX, 36, lane);
+        lz_wg_tiles<2, 2>(gw + 6, st + LZTS_GZ1, 32, st + LZTS_RD1, 32, lane);
+        lz_wg_tiles<1, 2>(gw + 10, st + LZTS_GDX, 4, st + LZTS_RD2, 32, lane);
+        lz_wg_tiles<2, 2, 5>(gw + 12, st + LZTS_GT0, 32, st + LZTS_GX, 32, lane);   // T0 (2 x 5): grid columns
+        lz_wg_tiles<2, 3, 5>(gw + 14, st + LZTS_GT0, 32, st + LZTS_EX, 36, lane);   //            frequency columns
+        lz_wg_tiles<2, 2>(gw + 22, st + LZTS_GT1, 32, st + LZTS_RT1, 32, lane);
+        lz_wg_tiles<1, 2>(gw + 26, st + LZTS_GO, 4, st + LZTS_RT2, 32, lane);
+        lz_wave_lds_sync();   // the next slice overwrites the rows just read
     }
-    // ---- the workgroup's four waves, summed in wave order, then one partial per workgroup ----
-    __syncthreads();
-    if (wave > 0) {
-        float* dst = stage + (wave - 1) * LZTG_ELEMS;
-#pragma unroll
-        for (int t = 0; t < LZTG_TILES; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) dst[t * 256 + r * 64 + lane] = gw[t][r];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float* out = partials + (size_t)blockIdx.x * LZTG_ELEMS;
-#pragma unroll
-        for (int t = 0; t < LZTG_TILES; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float v = gw[t][r];
-                for (int w = 0; w < 3; w++) v += stage[w * LZTG_ELEMS + t * 256 + r * 64 + lane];
-                out[t * 256 + r * 64 + lane] = v;
-            }
-    }
+    // ---- the waves folded in wave order into the staging rows, then one partial per workgroup ----
+    lz_wg_fold_and_store<LZTG_TILES, LZT_WG / 64>(gw, stage, partials + (size_t)blockIdx.x * LZTG_ELEMS, lane, wave);
 }
 
 // ---- combine: the workgroup partials in workgroup order -> the weight gradients; the frame-constant gradients ----------------------
@@ -353,25 +302,17 @@ __global__ void __launch_bounds__(256) lz_k_torso_train_combine(const float* __r
     constexpr int K0 = LZ_TORSO_FREQ + LZ_TORSO_ANCHOR + IND, K1 = LZ_TORSO_GRIDF + K0, H = LZ_TORSO_HID;
     __shared__ float red[4][64];
     __shared__ float sums[64];
-    const int slot = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int slot = threadIdx.x & 63;
     const bool last = blockIdx.x == LZTC_BLOCKS;
-    // element index of a tile (t) entry D[row][col] (lane 16 (row >> 2) + col, register row & 3)
-    auto elem = [](int t, int row, int col) { return t * 256 + (row & 3) * 64 + 16 * (row >> 2) + col; };
-    int e;
-    if (!last) e = blockIdx.x * 64 + slot;
-    else {   // slot o < 32: sum of deform layer 0's output gradient o (D0 tile (o >> 4, 2), column 2); o >= 32: torso layer 0's (T0 tile (., 4))
+    int e = blockIdx.x * 64 + slot;
+    if (last) {   // slot o < 32: sum of deform layer 0's output gradient o (D0 tile (o >> 4, 2), column 2); o >= 32: torso layer 0's (T0 tile (., 4))
         const int o = slot & 31;
-        e = slot < 32 ? elem((o >> 4) * 3 + 2, o & 15, 2) : elem(12 + (o >> 4) * 5 + 4, o & 15, 2);
+        e = slot < 32 ? lz_wg_elem((o >> 4) * 3 + 2, o & 15, 2) : lz_wg_elem(12 + (o >> 4) * 5 + 4, o & 15, 2);
     }
-    float v = 0.0f;
-    for (uint32_t g = part; g < n_groups; g += 4) v += partials[(size_t)g * LZTG_ELEMS + e];
-    red[part][slot] = v;
-    __syncthreads();
+    const float v = lz_wg_combine<LZTG_ELEMS>(partials, n_groups, e, red);
     if (!last) {
-        if (part != 0) return;
-        v = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
-        const int t = e >> 8, r = (e >> 6) & 3, l = e & 63;
-        const int row = 4 * (l >> 4) + r, col = l & 15;
+        if (threadIdx.x >= 64) return;
+        const auto [t, row, col] = lz_wg_elem(e);
         if (t < 6) {            // D0: per-pixel columns 0-33
             const int o = 16 * (t / 3) + row, k = 16 * (t % 3) + col;
             if (k < LZ_TORSO_FREQ) G.dw0[o * K0 + k] = v;
@@ -391,7 +332,7 @@ __global__ void __launch_bounds__(256) lz_k_torso_train_combine(const float* __r
         }
         return;
     }
-    if (part == 0) sums[slot] = ((red[0][slot] + red[1][slot]) + red[2][slot]) + red[3][slot];
+    if (threadIdx.x < 64) sums[slot] = v;
     __syncthreads();
     constexpr int KC = LZ_TORSO_ANCHOR + IND;
     for (int i = threadIdx.x; i < 2 * H * KC; i += 256) {   // weight columns of the constant inputs: sum_o x input_k
@@ -497,7 +438,7 @@ static LzTorsoTrainArgs lzt_train_args(const lz_torso_train_params* p) {
     return t;
 }
 
-extern "C" size_t lz_torso_train_workspace(void) { return (size_t)LZT_TRAIN_MAX_GROUPS * LZTG_ELEMS * sizeof(float); }
+extern "C" size_t lz_torso_train_workspace(void) { return lz_wg_workspace_bytes(LZTG_TILES); }
 
 extern "C" int lz_torso_train_forward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, float* alpha, float* color,
                                       float* deform, lz_stream_t stream) {
@@ -529,10 +470,7 @@ extern "C" int lz_torso_train_backward(const lz_torso_train_params* p, const flo
     const LzTorsoTrainArgs t = lzt_train_args(p);
     // one workgroup per CU (the staging rows and the 28 accumulator tiles fill the LDS and half the register file), at least four
     // slices per wave before the grid is full
-    uint32_t nwg = lz_div_up(N, 16 * 4 * (LZT_WG / 64));
-    uint32_t cap = (uint32_t)lz_cu_count();
-    if (cap > LZT_TRAIN_MAX_GROUPS) cap = LZT_TRAIN_MAX_GROUPS;
-    if (nwg > cap) nwg = cap;
+    const uint32_t nwg = lz_wg_grid(N, LZT_WG / 64, 1);
     float* part = static_cast<float*>(workspace);
     LzTorsoGradOut G{grads->g_deform_w0, grads->g_deform_w1, grads->g_deform_w2, grads->g_torso_w0, grads->g_torso_w1, grads->g_torso_w2,
                      grads->g_enc_anchor, grads->g_ind_code};

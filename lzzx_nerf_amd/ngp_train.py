@@ -14,23 +14,18 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
-from ._util import call, ptr, stream
+from ._util import as_f32, call, ptr, stream, workspace
 from .encoding import get_encoder
 from .linear import MLP
 from .ngp import GEO, HIDDEN, FusedHashgridNeRF, _check_shapes, _fragment_tables
 
 _SHAPES = [(HIDDEN, 32), (1 + GEO, HIDDEN), (HIDDEN, 16 + GEO), (3, HIDDEN)]
-_WS = {}
 _GATHER = {}
 
 
 def _workspace(device):
     """lz_ngp_train_workspace() bytes per device: per-workgroup partials, rewritten by every backward (no initialisation)"""
-    key = (device.type, device.index)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = _WS[key] = torch.empty(_lib.load().lz_ngp_train_workspace(), dtype=torch.uint8, device=device)
-    return ws
+    return workspace("ngp_train", device, _lib.load().lz_ngp_train_workspace())
 
 
 def _gather_index(device):
@@ -81,8 +76,7 @@ class _NgpTrain(Function):
             for g in gws:
                 g.zero_()
         else:
-            up = lambda t: None if t is None else t.float().contiguous()
-            g_sigma, g_rgb = up(g_sigma), up(g_rgb)
+            g_sigma, g_rgb = as_f32(g_sigma), as_f32(g_rgb)
             d_feats = torch.empty(16, M, 2, dtype=torch.float32, device=dev)
             call("lz_ngp_head_backward", ptr(packed), ptr(ws0), ptr(ws1), ptr(wc0), ptr(wc1), ptr(feats), ptr(dirs), M, None, ptr(g_sigma),
                  ptr(g_rgb), ptr(d_feats), *[ptr(g) for g in gws], ptr(_workspace(dev)), stream())

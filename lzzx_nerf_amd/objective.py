@@ -15,18 +15,11 @@ import torch
 from torch.autograd import Function
 
 from ._lib import LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE, LZ_OBJ_UNC, LZ_OBJECTIVE_WS_BYTES
-from ._util import call, ptr, stream
-
-_WS = {}
-
+from ._util import call, ptr, stream, workspace
 
 def _workspace(device):
     """LZ_OBJECTIVE_WS_BYTES per device, zeroed once (the kernels leave their tickets at 0); launches on it are ordered by the stream"""
-    key = (device.type, device.index)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = _WS[key] = torch.zeros(LZ_OBJECTIVE_WS_BYTES, dtype=torch.uint8, device=device)
-    return ws
+    return workspace("objective", device, LZ_OBJECTIVE_WS_BYTES, zero=True)
 
 
 def _rays(t, name, n_last, dtype=torch.float32):

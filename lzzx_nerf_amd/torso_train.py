@@ -16,7 +16,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
-from ._util import call, ptr, stream
+from ._util import as_f32, call, ptr, stream, workspace
 from .encoding import get_encoder
 from .linear import MLP
 
@@ -53,16 +53,9 @@ class TorsoTrainNet(nn.Module):
         return alpha, color, dx
 
 
-_WS = {}
-
-
 def _workspace(device):
     """lz_torso_train_workspace() bytes per device: per-workgroup partials, rewritten by every backward (no initialisation)"""
-    key = (device.type, device.index)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = _WS[key] = torch.empty(_lib.load().lz_torso_train_workspace(), dtype=torch.uint8, device=device)
-    return ws
+    return workspace("torso_train", device, _lib.load().lz_torso_train_workspace())
 
 
 class _AnchorEncode(Function):
@@ -113,8 +106,7 @@ class _TorsoTrain(Function):
             g = _lib.TorsoGrads()
             g.g_deform_w0, g.g_deform_w1, g.g_deform_w2, g.g_torso_w0, g.g_torso_w1, g.g_torso_w2 = [w.data_ptr() for w in ws]
             g.g_emb, g.g_enc_anchor, g.g_ind_code = g_emb.data_ptr(), g_enc.data_ptr(), g_ind.data_ptr() if g_ind is not None else None
-            up = lambda t: None if t is None else t.float().contiguous()
-            g_alpha, g_color, g_deform = up(g_alpha), up(g_color), up(g_deform)
+            g_alpha, g_color, g_deform = as_f32(g_alpha), as_f32(g_color), as_f32(g_deform)
             call("lz_torso_train_backward", C.byref(p), ptr(xy), N, ptr(g_alpha), ptr(g_color), ptr(g_deform), C.byref(g),
                  ptr(_workspace(xy.device)), stream())
         return (None, None, g_enc, g_ind) + tuple(ws) + (g_emb,)
