@@ -69,6 +69,24 @@ int lz_grid_encode_backward(const void* grad, const float* inputs, const void* e
                             const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, int emb_f16,
                             int grad_layout, lz_stream_t stream);
 
+/* The same table gradient WITHOUT float atomics, every entry summed in the CPU checker's order (gridencoder.cu:226-313 leaves the
+ * order of its atomicAdds open; oracle/grid_oracle.c fixes it): per entry, sequentially over (sample ascending, corner ascending),
+ * acc = acc + w * g in f32, starting from what grad_embeddings holds -- it adds onto the buffer like the atomic entry, and a batch cut
+ * into consecutive sample ranges, one call after the other, gives the bits of one call.  The same bits on every call and for every
+ * workspace size.  Per level: (entry, term rank) keys, a stable radix sort over the bits the level needs, a segmented sequential sum
+ * (csrc/lz_grid.hip).  Additive under ABI version 11.
+ * Arguments as lz_grid_encode_backward, except: grad_layout 0 = [L,B,C] or 1 = [B,L*C] only; f32 tables only (emb_f16 = 1 is
+ * LZ_ERR_UNSUPPORTED), D 2 or 3, C 1, 2, 4 or 8; workspace: device memory, 16-byte aligned, no initialisation, of
+ * workspace_bytes_lo + 2^32 * workspace_bytes_hi bytes.  lz_grid_ordered_workspace(B, D) bytes let a level of B samples run in one
+ * piece; with less the batch is processed in sample ranges that fit (LZ_ERR_BAD_ARGUMENT when not even one sample's 2^D terms do).
+ * dy_dx / grad_inputs as there (kernel_input_backward, gridencoder.cu:316-342, is a fixed order already). */
+size_t lz_grid_ordered_workspace(uint32_t B, uint32_t D);
+int lz_grid_encode_backward_ordered(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                    void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                    const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, int emb_f16,
+                                    int grad_layout, void* workspace, uint32_t workspace_bytes_lo, uint32_t workspace_bytes_hi,
+                                    lz_stream_t stream);
+
 /* test hook: flat table index of every corner, [L,B,2^D] i32 (-1 = out of range); exposes get_grid_index
  * (gridencoder.cu:54-72) so index parity can be asserted bit for bit */
 int lz_grid_corner_indices(const float* inputs, const int32_t* offsets, int32_t* corner_idx, uint32_t B, uint32_t D,

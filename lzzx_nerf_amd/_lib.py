@@ -87,6 +87,7 @@ class FrameNgp(C.Structure):
 SIGNATURES = {
     "lz_grid_encode_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, i32, i32, i32, vp],
     "lz_grid_encode_backward": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp],
+    "lz_grid_encode_backward_ordered": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp, u32, u32, vp],
     "lz_grid_corner_indices": [vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, vp],
     "lz_sh_encode_forward": [vp, vp, u32, u32, u32, vp, vp],
     "lz_sh_encode_backward": [vp, vp, u32, u32, u32, vp, vp, vp],
@@ -196,7 +197,8 @@ LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
-         "lz_audio_train_workspace": ([], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t)}
+         "lz_audio_train_workspace": ([], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
+         "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

@@ -33,12 +33,13 @@ def require_cuda(**tensors):
 _WS = {}
 
 
-def workspace(tag, device, nbytes, zero=False):
+def workspace(tag, device, nbytes, zero=False, grow=False):
     """a cached byte tensor per (tag, device): kernel scratch that lives across calls (zero: cleared once, when allocated).
+    grow: a request larger than the cached tensor replaces it (the old one is freed in stream order by torch's allocator).
     Launches on it are ordered by the stream; two streams at once would share it (not supported)"""
     key = (tag, device.type, device.index)
     ws = _WS.get(key)
-    if ws is None:
+    if ws is None or (grow and ws.numel() < nbytes):
         ws = _WS[key] = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=device)
     return ws
 

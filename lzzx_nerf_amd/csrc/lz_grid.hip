@@ -1213,3 +1213,324 @@ extern "C" int lz_grid_encode_backward(const void* grad, const float* inputs, co
     LZ_CHECK_LAUNCH("grid_encode_backward");
     return LZ_OK;
 }
+
+// ---- ordered table gradient: no float atomics, the CPU checker's summation order (gridencoder.cu:226-313) ---------------------------
+// The checker adds the terms of a table entry one after another over (level, sample ascending, corner ascending) with a plain f32
+// `+= w * g`.  Here a level's terms -- one per (sample b, corner idx), rank t = b * 2^D + idx -- are sorted by entry with a STABLE least-
+// significant-digit radix sort of (entry, t) pairs, 8 bits per pass over only the bits the level's size needs, so that the terms of one
+// entry end up next to each other in ascending t; then one thread per (entry, channel) walks its segment and adds w * g in that order,
+// starting from what the buffer holds (so a batch may be cut into sample ranges that run one after another: same bits, bounded
+// workspace).  w is recomputed from inputs[b] with the helpers above, g is read where the caller left it: no values are materialised.
+//
+// A pass is four launches.  hist: a wave owns a tile of LZ_ORD_TILE consecutive pairs and counts its digits in LDS (integer atomics).
+// scan / scan_totals: exclusive scan of the digit-major [256][tiles] counters (4096 per workgroup, then the workgroup totals).  scatter:
+// the wave walks its tile again, 64 pairs per step in order; the lanes of a step that hold the same digit find each other with eight
+// ballots, a lane's place is the digit's running base plus the number of lower lanes in its group, and the group's first lane moves the
+// base on -- ranks follow (step, lane), which is the order of the input, so the pass is stable.  The level's size lives in `offsets` on
+// the device, so the host always enqueues four passes and the ones past the level's bits return at once; the segment sum reads the
+// buffer the last live pass wrote.  Out-of-range samples get the key `size`, one past the last entry, which no segment reads.
+#define LZ_ORD_TILE 2048u      // pairs per wave and pass
+#define LZ_ORD_WAVES 4u        // waves (tiles) per workgroup of hist / scatter
+#define LZ_ORD_SCAN 4096u      // counters per workgroup of the scan
+#define LZ_ORD_PASSES 4u       // 32 key bits at most
+
+__device__ __forceinline__ uint32_t lz_ord_level_passes(const int* __restrict__ offsets, uint32_t level) {
+    const uint32_t hs = (uint32_t)offsets[level + 1] - (uint32_t)offsets[level];
+    const uint32_t bits = 32u - (uint32_t)__clz((int)hs);     // keys run from 0 to hs inclusive
+    return (bits + 7u) >> 3;
+}
+
+template <uint32_t D>
+__global__ void __launch_bounds__(256)
+lz_k_grid_ord_keys(const float* __restrict__ inputs, const int* __restrict__ offsets, uint2* __restrict__ pairs, uint32_t b0, uint32_t nB,
+                   uint32_t level, LzGridLevels lv, uint32_t gridtype, bool align_corners) {
+    const uint32_t bl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (bl >= nB) return;
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
+    float x[D];
+#pragma unroll
+    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)(b0 + bl) * D + d];
+    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+    uint32_t term[D][2];
+    lz_grid_terms<D>(lvl, cell, align_corners, term);
+    uint2* o = pairs + (size_t)bl * (1u << D);
+#pragma unroll
+    for (uint32_t idx = 0; idx < (1u << D); idx++) {
+        const uint32_t e = lz_grid_corner_index<D>(lvl, cell, term, idx, 1u, gridtype, align_corners);
+        o[idx] = make_uint2((cell.oob || e > lvl.hs) ? lvl.hs : e, (bl << D) | idx);
+    }
+}
+
+__global__ void __launch_bounds__(64 * LZ_ORD_WAVES)
+lz_k_grid_ord_hist(const uint2* __restrict__ pairs, const int* __restrict__ offsets, uint32_t level, uint32_t pass, uint32_t N, uint32_t nwt,
+                   uint32_t* __restrict__ counters) {
+    __shared__ uint32_t cnt[LZ_ORD_WAVES][256];
+    if (pass >= lz_ord_level_passes(offsets, level)) return;   // workgroup-uniform
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wt = blockIdx.x * LZ_ORD_WAVES + wave, shift = 8u * pass;
+    for (uint32_t k = lane; k < 256u; k += 64u) cnt[wave][k] = 0u;
+    __syncthreads();
+    if (wt < nwt) {
+        const uint32_t i0 = wt * LZ_ORD_TILE;
+        for (uint32_t s = 0; s < LZ_ORD_TILE / 64u && i0 + s * 64u < N; s++) {
+            const uint32_t i = i0 + s * 64u + lane;
+            if (i < N) atomicAdd(&cnt[wave][(pairs[i].x >> shift) & 255u], 1u);
+        }
+    }
+    __syncthreads();
+    if (wt < nwt)
+        for (uint32_t k = lane; k < 256u; k += 64u) counters[(size_t)k * nwt + wt] = cnt[wave][k];
+}
+
+// exclusive scan of one value per thread over a 1024-thread workgroup; sw: 17 words of LDS
+__device__ __forceinline__ uint32_t lz_ord_block_scan(uint32_t v, uint32_t* sw, uint32_t& total) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t n = (uint32_t)__shfl_up((int)inc, off, 64);
+        if (lane >= off) inc += n;
+    }
+    if (lane == 63u) sw[wave] = inc;
+    __syncthreads();
+    if (wave == 0u) {
+        const uint32_t w = lane < 16u ? sw[lane] : 0u;
+        uint32_t winc = w;
+#pragma unroll
+        for (uint32_t off = 1; off < 16u; off <<= 1) {
+            const uint32_t n = (uint32_t)__shfl_up((int)winc, off, 64);
+            if (lane >= off) winc += n;
+        }
+        if (lane < 16u) sw[lane] = winc - w;
+        if (lane == 15u) sw[16] = winc;
+    }
+    __syncthreads();
+    const uint32_t prefix = sw[wave] + inc - v;
+    total = sw[16];
+    __syncthreads();
+    return prefix;
+}
+
+__global__ void __launch_bounds__(1024)
+lz_k_grid_ord_scan(uint32_t* __restrict__ counters, uint32_t* __restrict__ totals, const int* __restrict__ offsets, uint32_t level,
+                   uint32_t pass, uint32_t M) {
+    __shared__ uint32_t sw[17];
+    if (pass >= lz_ord_level_passes(offsets, level)) return;
+    const uint32_t base = blockIdx.x * LZ_ORD_SCAN + threadIdx.x * 4u;
+    uint32_t v[4];
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) v[k] = base + k < M ? counters[base + k] : 0u;
+    uint32_t total;
+    uint32_t run = lz_ord_block_scan(v[0] + v[1] + v[2] + v[3], sw, total);
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        if (base + k < M) counters[base + k] = run;
+        run += v[k];
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(1024)
+lz_k_grid_ord_scan_totals(uint32_t* __restrict__ totals, const int* __restrict__ offsets, uint32_t level, uint32_t pass, uint32_t nblk) {
+    __shared__ uint32_t sw[17];
+    if (pass >= lz_ord_level_passes(offsets, level)) return;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nblk; base += 1024u) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < nblk ? totals[i] : 0u;
+        uint32_t total;
+        const uint32_t prefix = lz_ord_block_scan(v, sw, total);
+        if (i < nblk) totals[i] = carry + prefix;
+        carry += total;
+    }
+}
+
+__global__ void __launch_bounds__(64 * LZ_ORD_WAVES)
+lz_k_grid_ord_scatter(const uint2* __restrict__ in, uint2* __restrict__ out, const int* __restrict__ offsets, uint32_t level, uint32_t pass,
+                      uint32_t N, uint32_t nwt, const uint32_t* __restrict__ counters, const uint32_t* __restrict__ totals) {
+    __shared__ uint32_t base_s[LZ_ORD_WAVES][256];
+    if (pass >= lz_ord_level_passes(offsets, level)) return;   // workgroup-uniform
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, wt = blockIdx.x * LZ_ORD_WAVES + wave, shift = 8u * pass;
+    if (wt >= nwt) return;                                      // wave-uniform; no workgroup barrier below
+    volatile uint32_t* base = base_s[wave];                     // this wave's alone: written and read in program order by one wave
+    for (uint32_t k = lane; k < 256u; k += 64u) {
+        const uint32_t c = k * nwt + wt;
+        base[k] = counters[c] + totals[c / LZ_ORD_SCAN];
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t i0 = wt * LZ_ORD_TILE;
+    for (uint32_t s = 0; s < LZ_ORD_TILE / 64u && i0 + s * 64u < N; s++) {
+        const uint32_t i = i0 + s * 64u + lane;
+        const bool valid = i < N;
+        const uint2 p = valid ? in[i] : make_uint2(0u, 0u);
+        const uint32_t digit = (p.x >> shift) & 255u;
+        unsigned long long m = __ballot(valid);
+#pragma unroll
+        for (uint32_t bit = 0; bit < 8; bit++) {
+            const bool set = ((digit >> bit) & 1u) != 0u;
+            const unsigned long long bb = __ballot(set);
+            m &= set ? bb : ~bb;
+        }
+        const uint32_t rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        const uint32_t start = base[digit];
+        __builtin_amdgcn_wave_barrier();
+        if (valid && rank == 0u) base[digit] = start + (uint32_t)__popcll(m);
+        __builtin_amdgcn_wave_barrier();
+        if (valid) out[start + rank] = p;
+    }
+}
+
+template <uint32_t D, uint32_t C>
+__global__ void __launch_bounds__(256)
+lz_k_grid_ord_sum(const uint2* __restrict__ buf0, const uint2* __restrict__ buf1, const float* __restrict__ grad,
+                  const float* __restrict__ inputs, const int* __restrict__ offsets, float* __restrict__ grad_grid, uint32_t B, uint32_t L,
+                  uint32_t level, uint32_t b0, uint32_t N, LzGridLevels lv, uint32_t gridtype, bool align_corners, bool sample_major) {
+    const LzGridLevel lvl = lz_grid_level<D>(offsets, lv, level, gridtype, align_corners);
+    const uint2* __restrict__ pairs = (lz_ord_level_passes(offsets, level) & 1u) ? buf1 : buf0;
+    float* gg = grad_grid + (size_t)lvl.off0 * C;
+    const uint64_t total = (uint64_t)lvl.hs * C, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; gid < total; gid += stride) {
+        const uint32_t entry = (uint32_t)(gid / C), ch = (uint32_t)(gid - (uint64_t)entry * C);
+        uint32_t lo = 0, hi = N;                      // first pair of the entry
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (pairs[mid].x < entry) lo = mid + 1u;
+            else hi = mid;
+        }
+        if (lo >= N || pairs[lo].x != entry) continue;   // no term: the entry is not written
+        float acc = gg[gid];
+        for (uint32_t i = lo;; i += 4u) {
+            // four products in flight, added one after another: the sum itself is serial by definition
+            float p[4];
+            bool ok[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t j = i + k;
+                const bool in = j >= i && j < N;
+                const uint2 pr = in ? pairs[j] : make_uint2(0u, 0u);
+                ok[k] = in && pr.x == entry;
+                p[k] = 0.0f;
+                if (ok[k]) {
+                    const uint32_t b = b0 + (pr.y >> D), idx = pr.y & ((1u << D) - 1u);
+                    float x[D];
+#pragma unroll
+                    for (uint32_t d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
+                    const LzGridCell<D> cell = lz_grid_cell<D, false>(x, lvl.scale, align_corners);
+                    const float w = lz_grid_weight<D>(cell, idx);
+                    const float g = grad[(sample_major ? ((size_t)b * L + level) * C : ((size_t)level * B + b) * C) + ch];
+                    p[k] = w * g;
+                }
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (ok[k]) acc = acc + p[k];
+            if (!ok[3]) break;
+        }
+        gg[gid] = acc;
+    }
+}
+
+// workspace of one level of n terms: two pair buffers, the digit-major counters, the scan's workgroup totals (each 256-byte aligned)
+struct LzOrdLayout {
+    uint64_t buf1, counters, totals, bytes;
+    uint32_t nwt, M, nblk;
+};
+static LzOrdLayout lz_ord_layout(uint64_t n) {
+    LzOrdLayout l;
+    const uint64_t nwt = (n + LZ_ORD_TILE - 1) / LZ_ORD_TILE, M = 256u * nwt, nblk = (M + LZ_ORD_SCAN - 1) / LZ_ORD_SCAN;
+    auto up = [](uint64_t v) { return (v + 255u) & ~(uint64_t)255u; };
+    l.buf1 = up(8u * n);
+    l.counters = l.buf1 + up(8u * n);
+    l.totals = l.counters + up(4u * M);
+    l.bytes = l.totals + up(4u * (nblk + 1u));
+    l.nwt = (uint32_t)nwt, l.M = (uint32_t)M, l.nblk = (uint32_t)nblk;
+    return l;
+}
+
+extern "C" size_t lz_grid_ordered_workspace(uint32_t B, uint32_t D) {
+    if (D != 2u && D != 3u) return 0;
+    return (size_t)lz_ord_layout((uint64_t)B << D).bytes;
+}
+
+template <uint32_t D>
+static void lz_grid_ord_sum_launch(uint32_t C, dim3 grid, hipStream_t st, const uint2* buf0, const uint2* buf1, const float* grad,
+                                   const float* inputs, const int* offsets, float* gemb, uint32_t B, uint32_t L, uint32_t level, uint32_t b0,
+                                   uint32_t N, const LzGridLevels& lv, uint32_t gridtype, bool ac, bool sm) {
+    switch (C) {
+        case 1: hipLaunchKernelGGL((lz_k_grid_ord_sum<D, 1>), grid, dim3(256), 0, st, buf0, buf1, grad, inputs, offsets, gemb, B, L, level, b0, N, lv, gridtype, ac, sm); break;
+        case 2: hipLaunchKernelGGL((lz_k_grid_ord_sum<D, 2>), grid, dim3(256), 0, st, buf0, buf1, grad, inputs, offsets, gemb, B, L, level, b0, N, lv, gridtype, ac, sm); break;
+        case 4: hipLaunchKernelGGL((lz_k_grid_ord_sum<D, 4>), grid, dim3(256), 0, st, buf0, buf1, grad, inputs, offsets, gemb, B, L, level, b0, N, lv, gridtype, ac, sm); break;
+        default: hipLaunchKernelGGL((lz_k_grid_ord_sum<D, 8>), grid, dim3(256), 0, st, buf0, buf1, grad, inputs, offsets, gemb, B, L, level, b0, N, lv, gridtype, ac, sm); break;
+    }
+}
+
+template <uint32_t D>
+static void lz_grid_ord_run(const float* grad, const float* inputs, const int* offsets, float* gemb, uint32_t B, uint32_t C, uint32_t L,
+                            const LzGridLevels& lv, uint32_t gridtype, bool ac, bool sm, unsigned char* ws, uint32_t chunk, hipStream_t st) {
+    const dim3 sum_grid((uint32_t)lz_cu_count() * 8u);
+    for (uint32_t level = 0; level < L; level++) {
+        for (uint32_t b0 = 0; b0 < B; b0 += chunk) {      // sample ranges in order: each continues the sums of the one before
+            const uint32_t nB = B - b0 < chunk ? B - b0 : chunk, N = nB << D;
+            const LzOrdLayout lay = lz_ord_layout(N);
+            uint2* buf[2] = {reinterpret_cast<uint2*>(ws), reinterpret_cast<uint2*>(ws + lay.buf1)};
+            uint32_t* counters = reinterpret_cast<uint32_t*>(ws + lay.counters);
+            uint32_t* totals = reinterpret_cast<uint32_t*>(ws + lay.totals);
+            hipLaunchKernelGGL((lz_k_grid_ord_keys<D>), dim3(lz_div_up(nB, 256)), dim3(256), 0, st, inputs, offsets, buf[0], b0, nB, level, lv,
+                               gridtype, ac);
+            const dim3 tiles(lz_div_up(lay.nwt, LZ_ORD_WAVES)), wg(64 * LZ_ORD_WAVES);
+            for (uint32_t pass = 0; pass < LZ_ORD_PASSES; pass++) {
+                const uint2* in = buf[pass & 1u];
+                uint2* out = buf[(pass + 1u) & 1u];
+                hipLaunchKernelGGL(lz_k_grid_ord_hist, tiles, wg, 0, st, in, offsets, level, pass, N, lay.nwt, counters);
+                hipLaunchKernelGGL(lz_k_grid_ord_scan, dim3(lay.nblk), dim3(1024), 0, st, counters, totals, offsets, level, pass, lay.M);
+                hipLaunchKernelGGL(lz_k_grid_ord_scan_totals, dim3(1), dim3(1024), 0, st, totals, offsets, level, pass, lay.nblk);
+                hipLaunchKernelGGL(lz_k_grid_ord_scatter, tiles, wg, 0, st, in, out, offsets, level, pass, N, lay.nwt, counters, totals);
+            }
+            lz_grid_ord_sum_launch<D>(C, sum_grid, st, buf[0], buf[1], grad, inputs, offsets, gemb, B, L, level, b0, N, lv, gridtype, ac, sm);
+        }
+    }
+}
+
+extern "C" int lz_grid_encode_backward_ordered(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                               void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                               const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, int emb_f16,
+                                               int grad_layout, void* workspace, uint32_t workspace_bytes_lo, uint32_t workspace_bytes_hi,
+                                               lz_stream_t stream) {
+    (void)embeddings;
+    if (B == 0) return LZ_OK;
+    LZ_REQUIRE(grad && inputs && offsets && grad_embeddings && workspace, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: null tensor");
+    LZ_REQUIRE(L >= 1 && H >= 1 && gridtype <= 1u, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: num_levels and base_resolution must be >= 1, gridtype 0 (hash) or 1 (tiled)");
+    LZ_REQUIRE(grad_layout == 0 || grad_layout == 1, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: grad_layout must be 0 ([L, B, C]) or 1 ([B, L*C])");
+    LZ_REQUIRE(!grad_inputs || dy_dx, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: grad_inputs needs dy_dx");
+    LZ_REQUIRE(!emb_f16, LZ_ERR_UNSUPPORTED, "grid_encode_backward_ordered: f32 tables only (half tables take lz_grid_encode_backward)");
+    LZ_REQUIRE(D == 2u || D == 3u, LZ_ERR_UNSUPPORTED, "grid_encode_backward_ordered: D must be 2 or 3");
+    LZ_REQUIRE(C == 1u || C == 2u || C == 4u || C == 8u, LZ_ERR_UNSUPPORTED, "grid_encode_backward_ordered: C must be 1, 2, 4, or 8.");
+    LZ_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15u) == 0u, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: workspace must be 16-byte aligned");
+    LzGridLevels lv;
+    LZ_REQUIRE(lz_fill_levels(lv, L, S, H) == 0, LZ_ERR_UNSUPPORTED, "grid_encode_backward_ordered: at most %d levels", LZ_MAX_LEVELS);
+    // the largest sample range whose terms fit the workspace (and 31 bits): the result does not depend on it
+    const uint64_t ws_bytes = ((uint64_t)workspace_bytes_hi << 32) | workspace_bytes_lo;
+    uint64_t lo = 0, hi = B < (0x80000000u >> D) ? B : (0x80000000u >> D);
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (lz_ord_layout(mid << D).bytes <= ws_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    LZ_REQUIRE(lo >= 1, LZ_ERR_BAD_ARGUMENT, "grid_encode_backward_ordered: the workspace (%llu bytes) does not hold one sample's terms; lz_grid_ordered_workspace(B, D) sizes it",
+               (unsigned long long)ws_bytes);
+    const bool sm = grad_layout == 1, ac = align_corners != 0;
+    hipStream_t st = lz_st(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    if (D == 2u) lz_grid_ord_run<2>((const float*)grad, inputs, offsets, (float*)grad_embeddings, B, C, L, lv, gridtype, ac, sm, ws, (uint32_t)lo, st);
+    else lz_grid_ord_run<3>((const float*)grad, inputs, offsets, (float*)grad_embeddings, B, C, L, lv, gridtype, ac, sm, ws, (uint32_t)lo, st);
+    if (dy_dx && grad_inputs) {   // kernel_input_backward (gridencoder.cu:316-342): already a fixed order
+        const dim3 g(lz_div_up((uint64_t)B * D, 256)), blk(256);
+        const float *gr = (const float*)grad, *jac = (const float*)dy_dx;
+        float* gi = (float*)grad_inputs;
+#define LZ_ORD_GIN(DD, CC) hipLaunchKernelGGL((lz_k_grid_input_backward<float, DD, CC>), g, blk, 0, st, gr, jac, gi, B, L, sm)
+        if (D == 2u) { if (C == 1u) LZ_ORD_GIN(2, 1); else if (C == 2u) LZ_ORD_GIN(2, 2); else if (C == 4u) LZ_ORD_GIN(2, 4); else LZ_ORD_GIN(2, 8); }
+        else { if (C == 1u) LZ_ORD_GIN(3, 1); else if (C == 2u) LZ_ORD_GIN(3, 2); else if (C == 4u) LZ_ORD_GIN(3, 4); else LZ_ORD_GIN(3, 8); }
+#undef LZ_ORD_GIN
+    }
+    LZ_CHECK_LAUNCH("grid_encode_backward_ordered");
+    return LZ_OK;
+}

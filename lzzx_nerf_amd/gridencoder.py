@@ -10,9 +10,45 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from ._util import call, ptr, require_cuda, stream
+from . import _lib
+from ._util import call, ptr, require_cuda, stream, workspace
 
 _gridtype_to_id = {"hash": 0, "tiled": 1}
+
+# How the table gradient is summed: "atomic" = float atomics (the reference's way: repeatable only up to summation order), "ordered" =
+# lz_grid_encode_backward_ordered: no float atomics, every entry summed in the CPU checker's (sample, corner) order, the same bits on
+# every call (f32 tables, D 2 / 3).
+_TABLE_GRADS = ("atomic", "ordered")
+_TABLE_GRAD = "atomic"
+ORDERED_WORKSPACE_CAP = 256 << 20   # bytes; a batch whose level needs more is processed in sample ranges (same bits)
+
+
+def set_table_grad(mode):
+    """module default for the table gradient of grid_encode / GridEncoder, FusedHashgridTrainNeRF(table_grad=None) and the f32 training
+    head's per-plane scatter; returns the previous one"""
+    global _TABLE_GRAD
+    if mode not in _TABLE_GRADS:
+        raise ValueError("table_grad must be one of %s, got %r" % (_TABLE_GRADS, mode))
+    prev, _TABLE_GRAD = _TABLE_GRAD, mode
+    return prev
+
+
+def table_grad():
+    return _TABLE_GRAD
+
+
+def grid_backward_ordered(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners,
+                          grad_layout, workspace_bytes=None):
+    """lz_grid_encode_backward_ordered on a per-device cached workspace of min(what one level of B samples needs, ORDERED_WORKSPACE_CAP)
+    bytes (the cache keeps the largest size asked for so far); workspace_bytes overrides the size"""
+    need = int(_lib.load().lz_grid_ordered_workspace(B, D))
+    if need == 0:
+        raise RuntimeError("the ordered table gradient is built for input_dim 2 and 3 (got %d)" % D)
+    nbytes = min(need, ORDERED_WORKSPACE_CAP) if workspace_bytes is None else int(workspace_bytes)
+    ws = workspace("grid_ordered", grad_embeddings.device, nbytes, grow=True)
+    call("lz_grid_encode_backward_ordered", ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_embeddings), B, D, C, L, S, H,
+         ptr(dy_dx), ptr(grad_inputs), int(gridtype), int(bool(align_corners)), int(embeddings.dtype == torch.float16), grad_layout,
+         ptr(ws), nbytes & 0xFFFFFFFF, nbytes >> 32, stream())
 
 
 def _check_dc(D, C):
@@ -92,6 +128,13 @@ class _grid_encode(Function):
         # small f32 tables + large batches: per-level accumulation in LDS instead of scattered global atomics
         glayout = 2 if (ctx.small_levels and B >= 16384 and embeddings.dtype == torch.float32) else 1
         grad_inputs = torch.zeros_like(inputs, dtype=embeddings.dtype) if dy_dx is not None else None
+        if _TABLE_GRAD == "ordered":
+            if embeddings.dtype != torch.float32:
+                raise RuntimeError("set_table_grad('ordered') sums f32 tables only; half tables (autocast with an even level_dim) take the "
+                                   "atomic path: set_table_grad('atomic') or leave autocast")
+            grid_backward_ordered(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                                  ctx.align_corners, 1)
+            return grad_inputs, grad_embeddings, None, None, None, None, None, None
         call("lz_grid_encode_backward", ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_embeddings), B, D, C, L,
              S, H, ptr(dy_dx), ptr(grad_inputs), int(gridtype), int(bool(ctx.align_corners)),
              int(embeddings.dtype == torch.float16), glayout, stream())

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, gridencoder
 from ._util import call, ptr, stream
 from .gridencoder import GridEncoder
 from .linear import MLP
@@ -224,8 +224,11 @@ class _FusedHeadTrain(Function):
                 jac, gin, feat = torch.empty(M, 24, **kw), torch.zeros(M, 2, **kw), torch.empty(12, M, 1, **kw)
                 call("lz_grid_encode_forward", ptr(c), ptr(e), ptr(mod.offsets), ptr(feat), M, 2, 1, 12, mod.S, mod.H, ptr(jac), 0, 0, 0, 0, stream())
                 dx01.append(gin)
-            call("lz_grid_encode_backward", ptr(g), ptr(c), ptr(e), ptr(mod.offsets), ptr(ge), M, 2, 1, 12, mod.S, mod.H, ptr(jac), ptr(gin), 0, 0,
-                 0, 3 if M >= 16384 else 0, stream())
+            if gridencoder.table_grad() == "ordered":   # no float atomics, the checker's order (gridencoder.set_table_grad)
+                gridencoder.grid_backward_ordered(g, c, e, mod.offsets, ge, M, 2, 1, 12, mod.S, mod.H, jac, gin, 0, False, 0)
+            else:
+                call("lz_grid_encode_backward", ptr(g), ptr(c), ptr(e), ptr(mod.offsets), ptr(ge), M, 2, 1, 12, mod.S, mod.H, ptr(jac), ptr(gin),
+                     0, 0, 0, 3 if M >= 16384 else 0, stream())
             demb.append(ge)
         if mod.keep_denc:
             mod.last_denc = denc

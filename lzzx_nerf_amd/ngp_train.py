@@ -4,7 +4,8 @@ rgb = sigmoid) as an autograd Function over fused kernels instead of ~25 operato
 
     forward   lz_grid_encode_forward_tiled (level-major gather, tiled f32 features) -> lz_ngp_head_forward (csrc/lz_ngp.hip)
     backward  lz_ngp_head_backward (csrc/lz_ngp_train.hip: recomputes the head, every MLP gradient on the matrix cores, a fixed-order
-              combine of the weight gradients) -> lz_grid_encode_backward (grad_layout 0: the table scatter, float atomics)
+              combine of the weight gradients) -> lz_grid_encode_backward (grad_layout 0: the table scatter, float atomics), or with
+              table_grad "ordered" lz_grid_encode_backward_ordered (no float atomics, the CPU checker's summation order)
 
 Scope: f32 arithmetic and f32 tables at the fixed cfg2 shape; no position / direction gradient.  What is not built is refused with an
 error, never answered with a silently wrong gradient."""
@@ -13,7 +14,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, gridencoder
 from ._util import as_f32, call, ptr, stream, workspace
 from .encoding import get_encoder
 from .linear import MLP
@@ -82,8 +83,12 @@ class _NgpTrain(Function):
                  ptr(g_rgb), ptr(d_feats), *[ptr(g) for g in gws], ptr(_workspace(dev)), stream())
             # the gather's own mapping, (x + bound) / (2 bound) in f32 (a true division: torch divides by a host scalar as a reciprocal multiply)
             unit = (xyzs + meta["bound"]) / torch.full((1,), 2.0 * meta["bound"], dtype=torch.float32, device=dev)
-            call("lz_grid_encode_backward", ptr(d_feats), ptr(unit), ptr(emb), ptr(meta["offsets"]), ptr(g_emb), M, 3, 2, 16, meta["S"], meta["H"],
-                 None, None, 0, 0, 0, 0, stream())
+            if (meta["table_grad"] or gridencoder.table_grad()) == "ordered":
+                gridencoder.grid_backward_ordered(d_feats, unit, emb, meta["offsets"], g_emb, M, 3, 2, 16, meta["S"], meta["H"], None, None, 0,
+                                                  False, 0)
+            else:
+                call("lz_grid_encode_backward", ptr(d_feats), ptr(unit), ptr(emb), ptr(meta["offsets"]), ptr(g_emb), M, 3, 2, 16, meta["S"],
+                     meta["H"], None, None, 0, 0, 0, 0, stream())
         return (None, None, None, g_emb) + tuple(gws)
 
 
@@ -100,14 +105,22 @@ class FusedHashgridTrainNeRF(nn.Module):
     state-dict keys are theirs (`encoder.embeddings`, `encoder.offsets`, `sigma_net.net.{0,1}.weight`, `color_net.net.{0,1}.weight`), so
     the modules of a `synthetic.GenericHashgridNeRF` load as they are, or are passed in and shared.  Every call reads the live parameter
     tensors (writes through `.data`, as an EMA swap-in does, are seen).  forward(xyzs, dirs, bound) gives `ngp.FusedHashgridNeRF`'s bits
-    for sigma and rgb.  The backward returns the table gradient (float atomics: repeatable only up to summation order) and the four weight
-    gradients (a fixed-order reduction: the same bits on every call, exactly linear in the upstream gradient, so GradScaler's powers of
-    two pass through).  No host synchronisation.
+    for sigma and rgb.  The backward returns the table gradient and the four weight gradients (a fixed-order reduction: the same bits on
+    every call, exactly linear in the upstream gradient, so GradScaler's powers of two pass through).  No host synchronisation.
+
+    table_grad: how the table gradient is summed.  "atomic" = float atomics, repeatable only up to summation order; "ordered" = every
+    table entry summed without atomics in the CPU checker's (sample, corner) order.  With "ordered" the whole backward repeats bit for
+    bit -- `encoder.embeddings.grad` and the four weight gradients are the same bits on every call from the same inputs, and the table
+    gradient equals oracle.grid_encode_backward on the d_feats of the backward -- at the price of a sort per level.  None (the default)
+    follows gridencoder.set_table_grad, read at every backward.
 
     Refused: inputs that require grad (no position / direction gradient), autocast, half tables, other encoder or MLP shapes."""
 
-    def __init__(self, encoder=None, sigma_net=None, color_net=None):
+    def __init__(self, encoder=None, sigma_net=None, color_net=None, table_grad=None):
         super().__init__()
+        if table_grad is not None and table_grad not in gridencoder._TABLE_GRADS:
+            raise ValueError("table_grad must be None or one of %s, got %r" % (gridencoder._TABLE_GRADS, table_grad))
+        self.table_grad = table_grad
         if encoder is None:
             encoder, _ = get_encoder("hashgrid")
         _check_encoder(encoder)
@@ -145,7 +158,8 @@ class FusedHashgridTrainNeRF(nn.Module):
         dirs = dirs.reshape(-1, 3).to(dev, torch.float32).contiguous()
         if dirs.shape[0] != xyzs.shape[0]:
             raise RuntimeError("FusedHashgridTrainNeRF: xyzs and dirs hold different numbers of points")
-        meta = dict(offsets=self.encoder.offsets.to(dev, torch.int32).contiguous(), bound=float(bound), S=self._S, H=self._H)
+        meta = dict(offsets=self.encoder.offsets.to(dev, torch.int32).contiguous(), bound=float(bound), S=self._S, H=self._H,
+                    table_grad=self.table_grad)
         return _NgpTrain.apply(meta, xyzs, dirs, emb.contiguous(), *[w.contiguous() for w in ws])
 
     def to_inference(self, precision="f32"):
