@@ -87,6 +87,40 @@ int lz_grid_encode_backward_ordered(const void* grad, const float* inputs, const
                                     int grad_layout, void* workspace, uint32_t workspace_bytes_lo, uint32_t workspace_bytes_hi,
                                     lz_stream_t stream);
 
+/* lz_grid_encode_backward_ordered over the rows of a WIDER sample-major matrix: row b of the gradient starts at
+ * grad + b * grad_row_stride elements (a multiple of C, >= L * C), so an [B, L*C] block of columns is summed where it lies -- the
+ * three-plane encoder below hands each plane's 12 columns of its [B, 36] gradient this way, without a slicing copy.  Table gradient
+ * only (no dy_dx / grad_inputs), f32 tables, sample-major; everything else, and the bits, as lz_grid_encode_backward_ordered.
+ * Additive under ABI version 11. */
+int lz_grid_encode_backward_ordered_strided(const void* grad, uint32_t grad_row_stride, const float* inputs, const int32_t* offsets,
+                                            void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                            uint32_t gridtype, int align_corners, void* workspace, uint32_t workspace_bytes_lo,
+                                            uint32_t workspace_bytes_hi, lz_stream_t stream);
+
+/* The triplane position encoder as one operator (csrc/lz_triplane_enc.hip).  Additive under ABI version 11.
+ * Replaces NeRFNetwork.encode_x, nerf_triplane/network.py:208-223 (split_xyz, three GridEncoder calls, torch.cat), and per plane the
+ * Python side of the operator, gridencoder/grid.py:18-84 (the [0, 1] mapping of grid.py:143 included), for three D = 2, C = 1, f32,
+ * hash-gridtype, align_corners = False encoders that share num_levels L <= 16, base resolution H, S = log2(per_level_scale) and
+ * `offsets` [L+1] i32.
+ * forward: xyz [B,3] f32 in [-bound, bound]; out [B,3L] f32 (16-byte aligned), columns xy | yz | xz, each level-major: the bits of
+ *   cat(enc_xy(x[:, :2]), enc_yz(x[:, 1:]), enc_xz(x[:, [0, 2]])).  The mapping is (x + bound) * (1.0f / (2 bound)), torch's two
+ *   roundings for a scalar divisor.  A coordinate outside [0, 1] after it zeroes the 12 features of the planes that use it
+ *   (gridencoder.cu:98-122).  dy_dx [3,B,L,2] f32 (8-byte aligned) or NULL: the per-plane Jacobians of gridencoder.cu:179-222.  One
+ *   launch; a wave's 64 rows leave as 16-byte stores over whole lines, and nothing is written past row B.
+ * backward: grad [B,3L] f32, read in place.  grad_emb_xy / _yz / _xz [sO] f32: the three tables' gradients, pre-zeroed by the caller
+ *   and accumulated with float atomics (B >= 16384: per (plane, level, chunk) in 64-bit fixed-point LDS first, as
+ *   lz_grid_encode_backward's layout 2) in one launch over all 3 L (plane, level) pairs; all three, or all NULL to skip them (a caller
+ *   that takes the ordered sum per plane from lz_grid_encode_backward_ordered_strided).  dy_dx + grad_xyz [B,3] (both or neither):
+ *   per plane kernel_input_backward's sum (gridencoder.cu:316-342) times 1 / (2 bound), then
+ *   d_x = g_xy[0] + g_xz[0], d_y = g_xy[1] + g_yz[0], d_z = g_yz[1] + g_xz[1], added in that order.
+ * B = 0 is LZ_OK without a launch; a null array, L outside 1 .. 16, H = 0 or a bound that is not positive and finite is
+ * LZ_ERR_BAD_ARGUMENT. */
+int lz_triplane_encode_forward(const float* xyz, const float* emb_xy, const float* emb_yz, const float* emb_xz, const int32_t* offsets,
+                               float* out, float* dy_dx, uint32_t B, uint32_t L, float S, uint32_t H, float bound, lz_stream_t stream);
+int lz_triplane_encode_backward(const float* grad, const float* xyz, const int32_t* offsets, float* grad_emb_xy, float* grad_emb_yz,
+                                float* grad_emb_xz, const float* dy_dx, float* grad_xyz, uint32_t B, uint32_t L, float S, uint32_t H,
+                                float bound, lz_stream_t stream);
+
 /* test hook: flat table index of every corner, [L,B,2^D] i32 (-1 = out of range); exposes get_grid_index
  * (gridencoder.cu:54-72) so index parity can be asserted bit for bit */
 int lz_grid_corner_indices(const float* inputs, const int32_t* offsets, int32_t* corner_idx, uint32_t B, uint32_t D,

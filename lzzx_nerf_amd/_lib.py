@@ -88,6 +88,10 @@ SIGNATURES = {
     "lz_grid_encode_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, i32, i32, i32, vp],
     "lz_grid_encode_backward": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp],
     "lz_grid_encode_backward_ordered": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp, u32, u32, vp],
+    "lz_grid_encode_backward_ordered_strided": [vp, u32, vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, vp, u32, u32, vp],
+    # the three-plane encoder (csrc/lz_triplane_enc.hip, lzzx_nerf_amd/gridencoder.py: TriplaneEncoder)
+    "lz_triplane_encode_forward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, u32, f32, vp],
+    "lz_triplane_encode_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, u32, f32, vp],
     "lz_grid_corner_indices": [vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, vp],
     "lz_sh_encode_forward": [vp, vp, u32, u32, u32, vp, vp],
     "lz_sh_encode_backward": [vp, vp, u32, u32, u32, vp, vp, vp],

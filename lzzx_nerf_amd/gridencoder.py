@@ -199,3 +199,109 @@ class GridEncoder(nn.Module):
         feats = grid_encode(rows, self.embeddings, self.offsets, self.per_level_scale, self.base_resolution, rows.requires_grad,
                             self.gridtype_id, self.align_corners)
         return feats.view(*inputs.shape[:-1], self.output_dim)
+
+
+class _triplane_encode(Function):
+    """xyz [B, 3] -> [B, 3 L] through lz_triplane_encode_forward / _backward: one launch each way, gradients for the three tables and,
+    when asked for, xyz.  With level_dim 1 the tables stay f32 under autocast (grid.py:28,38-39), so the output is f32 there as well."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, xyz, emb_xy, emb_yz, emb_xz, offsets, L, S, H, bound):
+        xyz = xyz.float().contiguous()
+        B = xyz.shape[0]
+        tables = [e.contiguous() for e in (emb_xy, emb_yz, emb_xz)]
+        require_cuda(xyz=xyz, embeddings_xy=tables[0], embeddings_yz=tables[1], embeddings_xz=tables[2], offsets=offsets)
+        out = torch.empty(B, 3 * L, device=xyz.device, dtype=torch.float32)
+        dy_dx = torch.empty(3, B, L, 2, device=xyz.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        call("lz_triplane_encode_forward", ptr(xyz), ptr(tables[0]), ptr(tables[1]), ptr(tables[2]), ptr(offsets), ptr(out), ptr(dy_dx), B, L, S,
+             H, bound, stream())
+        ctx.save_for_backward(xyz, offsets, dy_dx, *tables)
+        ctx.dims = (B, L, S, H, bound)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad):
+        xyz, offsets, dy_dx, *tables = ctx.saved_tensors
+        B, L, S, H, bound = ctx.dims
+        grad = grad.contiguous()                       # [B, 3 L], read in place by every kernel below: no per-plane slices
+        if grad.dtype != torch.float32:
+            grad = grad.float()
+        want_tables = any(ctx.needs_input_grad[1:4])
+        g_tables = [torch.zeros_like(t) for t in tables] if want_tables else [None] * 3
+        g_xyz = torch.empty_like(xyz) if dy_dx is not None else None
+        ordered = _TABLE_GRAD == "ordered" and want_tables and B > 0
+        if ordered:
+            # the checker's summation order per plane (lz_grid_encode_backward_ordered_strided); the plane's [0, 1] coordinates as the
+            # three-encoder path forms them
+            unit = (xyz + bound) / (2 * bound)
+            need = int(_lib.load().lz_grid_ordered_workspace(B, 2))
+            nbytes = min(need, ORDERED_WORKSPACE_CAP)
+            ws = workspace("grid_ordered", xyz.device, nbytes, grow=True)
+            for plane, cols in enumerate(((0, 1), (1, 2), (0, 2))):
+                uv = unit[:, cols].contiguous()
+                call("lz_grid_encode_backward_ordered_strided", grad.data_ptr() + 4 * plane * L, 3 * L, ptr(uv), ptr(offsets), ptr(g_tables[plane]),
+                     B, 2, 1, L, S, H, 0, 0, ptr(ws), nbytes & 0xFFFFFFFF, nbytes >> 32, stream())
+        if (want_tables and not ordered) or g_xyz is not None:
+            gt = [None] * 3 if ordered else g_tables
+            call("lz_triplane_encode_backward", ptr(grad), ptr(xyz), ptr(offsets), ptr(gt[0]), ptr(gt[1]), ptr(gt[2]), ptr(dy_dx), ptr(g_xyz), B, L,
+                 S, H, bound, stream())
+        return (g_xyz, g_tables[0], g_tables[1], g_tables[2], None, None, None, None, None)
+
+
+class TriplaneEncoder(nn.Module):
+    """NeRFNetwork.encode_x (network.py:208-223) as one operator: `xyz [B, 3]` in `[-bound, bound]` -> `[B, 3 L]`, the bits of
+    `cat([encoder_xy(xyz[:, :2]), encoder_yz(xyz[:, 1:]), encoder_xz(xyz[:, [0, 2]])], -1)` in one launch, and one launch back.
+
+    The three `GridEncoder`s are held in a plain tuple: not registered as submodules, their parameters not copied.  A network that
+    adds `self.encoder_xyz = TriplaneEncoder(self.encoder_xy, self.encoder_yz, self.encoder_xz)` keeps its state_dict keys,
+    parameters() and optimizer groups; gradients arrive in the three encoders' own `embeddings`."""
+
+    def __init__(self, encoder_xy, encoder_yz, encoder_xz):
+        super().__init__()
+        encoders = (encoder_xy, encoder_yz, encoder_xz)
+        self._check(encoders)
+        object.__setattr__(self, "encoders", encoders)      # past nn.Module.__setattr__ on purpose (a tuple is not registered anyway)
+        self.num_levels = encoder_xy.num_levels
+        self.output_dim = 3 * encoder_xy.num_levels
+
+    @staticmethod
+    def _check(encoders):
+        names = ("encoder_xy", "encoder_yz", "encoder_xz")
+        for name, enc in zip(names, encoders):
+            for field, want in (("input_dim", 2), ("level_dim", 1), ("gridtype", "hash"), ("align_corners", False)):
+                if getattr(enc, field) != want:
+                    raise RuntimeError("TriplaneEncoder: %s.%s must be %r, got %r" % (name, field, want, getattr(enc, field)))
+            if not 1 <= enc.num_levels <= 16:
+                raise RuntimeError("TriplaneEncoder: %s.num_levels must be 1 .. 16, got %r" % (name, enc.num_levels))
+        first = encoders[0]
+        for name, enc in zip(names[1:], encoders[1:]):
+            for field in ("num_levels", "base_resolution", "per_level_scale"):
+                if getattr(enc, field) != getattr(first, field):
+                    raise RuntimeError("TriplaneEncoder: %s.%s = %r differs from encoder_xy.%s = %r"
+                                       % (name, field, getattr(enc, field), field, getattr(first, field)))
+            if enc.offsets.shape != first.offsets.shape or not torch.equal(enc.offsets.cpu(), first.offsets.cpu()):
+                raise RuntimeError("TriplaneEncoder: %s.offsets differs from encoder_xy.offsets" % name)
+
+    def _check_tables(self):
+        # dtype and device can change after construction (.half(), .to(device)): looked at per call, metadata only
+        first = self.encoders[0].embeddings
+        for name, enc in zip(("encoder_xy", "encoder_yz", "encoder_xz"), self.encoders):
+            if enc.embeddings.dtype != torch.float32:
+                raise RuntimeError("TriplaneEncoder: %s.embeddings dtype must be torch.float32, got %s" % (name, enc.embeddings.dtype))
+            if enc.embeddings.device != first.device or enc.offsets.device != first.device:
+                raise RuntimeError("TriplaneEncoder: %s.embeddings device %s / offsets device %s differ from encoder_xy's device %s"
+                                   % (name, enc.embeddings.device, enc.offsets.device, first.device))
+
+    def extra_repr(self):
+        return "3 x (%s) -> %d" % (self.encoders[0].extra_repr(), self.output_dim)
+
+    def forward(self, xyz, bound=1):
+        self._check_tables()
+        exy, eyz, exz = self.encoders
+        rows = xyz.reshape(-1, 3)
+        S = float(np.float32(np.log2(exy.per_level_scale)))
+        feats = _triplane_encode.apply(rows, exy.embeddings, eyz.embeddings, exz.embeddings, exy.offsets, exy.num_levels, S,
+                                       int(exy.base_resolution), float(bound))
+        return feats.view(*xyz.shape[:-1], self.output_dim)
