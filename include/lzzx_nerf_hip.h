@@ -882,6 +882,46 @@ int lz_ngp_head_forward_f16(const void* packed16, const void* feats, int feat_la
                             float* sigmas, float* rgbs, lz_stream_t stream);
 /* lz_ngp_loop_run with lz_ngp_head_forward_f16 as the head (f->packed is not read); requires f->emb_f16 == 1 */
 int lz_ngp_loop_run_f16(const lz_frame_ngp* f, const void* packed16, uint32_t parity, uint32_t n_iterations, lz_stream_t stream);
+/* The whole hash-grid NeRF frame as ONE persistent kernel (csrc/lz_ngp_frame.hip): lz_frame_render's slot / refill design and cap
+ * semantics (see lz_frame_fused) around the network of lz_ngp_head_forward / lz_ngp_head_forward_f16, one sample per ray and pass; the
+ * 16-level gather runs inside the kernel, so no per-sample buffer exists.  Pixels, depth, sums and (with ray_counts) marched counts are
+ * lz_ngp_loop_run's bit for bit: under cap_mode 1 for the schedule whose ray budget is N_total (0 = N: the reference's; N *
+ * budget_factor for a fatter one; the step cap is the reference's 8), under cap_mode 0 for every ray that ends before max_steps (a ray
+ * alive there stops at max_steps samples).  Additive under ABI version 11.
+ * precision 0: the f32 head on `packed`, tables f32 (emb_f16 = 0) or half (1); precision 1: the f16 head on `packed16`, half tables.
+ * The caller owns every buffer; no allocation, no host synchronisation.  N == 0: LZ_OK, nothing launched.  State words as lz_frame_render
+ * ([1] [3] [5] [6] [9] [10] [11] [72]). */
+typedef struct {
+    const float* packed;           /* precision 0: LZ_NGP_FRAGS * 64 floats */
+    const void* packed16;          /* precision 1: LZ_NGP_PACKED_F16_BYTES */
+    uint32_t precision;            /* 0 = f32 head, 1 = f16 head (autocast arithmetic, needs emb_f16 = 1) */
+    int32_t emb_f16;               /* table type: 0 = f32, 1 = half */
+    const void* embeddings;        /* hash table [offsets[L], 2] */
+    const int32_t* offsets;        /* [L + 1] */
+    uint32_t enc_L, enc_H;         /* num_levels (16), base_resolution */
+    float enc_S;                   /* log2(per_level_scale) */
+    uint32_t cap_mode;             /* LZ_FRAME_CAP_PER_RAY | LZ_FRAME_CAP_REFERENCE */
+    const float* rays_o;  const float* rays_d;      /* [N,3] each */
+    const uint8_t* grid;           /* density bitfield */
+    const float* aabb;             /* [6] */
+    float* nears;  float* fars;    /* [N] each, written */
+    float* rays_t;                 /* [N] scratch */
+    int32_t* order;                /* [N] scratch: the queue */
+    int32_t* state;                /* LZ_FRAME_STATE_INTS, zeroed by the call */
+    uint8_t* keys;                 /* [N] scratch */
+    float* scratch;                /* [N] scratch */
+    float* weights_sum;  float* depth;  float* image;                     /* [N] [N] [N,3] */
+    float* out;                    /* [N,3] clamp(image + (1 - weights_sum) * bg, 0, 1) */
+    const float* bg;               /* [N,3] or NULL -> bg_scalar */
+    int32_t* ray_counts;           /* [N] or NULL: marched samples per ray */
+    int32_t* ray_last;             /* cap_mode 1: [N] scratch */
+    int32_t* cap_ws;               /* cap_mode 1: LZ_FRAME_CAP_WS_INTS(max_steps) int32 scratch */
+    float bg_scalar, bound, dt_gamma, T_thresh, min_near;
+    uint32_t N, max_steps, C, H;
+    uint32_t N_total;              /* cap_mode 1: ray budget of the schedule n_step = max(min(N_total / n_alive, 8), 1); 0 = N */
+} lz_frame_ngp_fused;
+/* `timing` (may be NULL): one event pair around the phase-1 persistent launch, as lz_frame_render */
+int lz_ngp_frame_render(const lz_frame_ngp_fused* f, struct lz_timing* timing, lz_stream_t stream);
 /* ---- Hash-grid NeRF training (lzzx_nerf_amd/ngp_train.py, FusedHashgridTrainNeRF; csrc/lz_ngp_train.hip) ----------------------
  * Additive under ABI version 11: new entries only.  Replaces the backward of sigma_net / color_net under autograd (network.py:73-94:
  * Linear, ReLU, cat with the SH features, exp, sigmoid).  The forward is lz_ngp_head_forward on tiled f32 features (feat_layout 1).

@@ -74,6 +74,15 @@ class FrameFused(C.Structure):
                 ("cap_mode", u32), ("N_total", u32), ("defer_finish", u32), ("ray_last", vp), ("cap_ws", vp)]
 
 
+class FrameNgpFused(C.Structure):
+    """mirror of lz_frame_ngp_fused (include/lzzx_nerf_hip.h)"""
+    _fields_ = [("packed", vp), ("packed16", vp), ("precision", u32), ("emb_f16", i32), ("embeddings", vp), ("offsets", vp), ("enc_L", u32),
+                ("enc_H", u32), ("enc_S", f32), ("cap_mode", u32), ("rays_o", vp), ("rays_d", vp), ("grid", vp), ("aabb", vp), ("nears", vp),
+                ("fars", vp), ("rays_t", vp), ("order", vp), ("state", vp), ("keys", vp), ("scratch", vp), ("weights_sum", vp), ("depth", vp),
+                ("image", vp), ("out", vp), ("bg", vp), ("ray_counts", vp), ("ray_last", vp), ("cap_ws", vp), ("bg_scalar", f32), ("bound", f32),
+                ("dt_gamma", f32), ("T_thresh", f32), ("min_near", f32), ("N", u32), ("max_steps", u32), ("C", u32), ("H", u32), ("N_total", u32)]
+
+
 class FrameNgp(C.Structure):
     """mirror of lz_frame_ngp (include/lzzx_nerf_hip.h)"""
     _fields_ = [("packed", vp), ("embeddings", vp), ("offsets", vp), ("enc_L", u32), ("enc_H", u32), ("enc_S", f32), ("emb_f16", i32), ("feats", vp),
@@ -143,6 +152,7 @@ SIGNATURES = {
     "lz_ngp_loop_run": [C.POINTER(FrameNgp), u32, u32, vp],
     "lz_ngp_head_forward_f16": [vp, vp, i32, vp, u32, vp, vp, vp, vp],
     "lz_ngp_loop_run_f16": [C.POINTER(FrameNgp), vp, u32, u32, vp],
+    "lz_ngp_frame_render": [C.POINTER(FrameNgpFused), vp, vp],
     # hash-grid NeRF training (csrc/lz_ngp_train.hip, lzzx_nerf_amd/ngp_train.py)
     "lz_ngp_head_backward": [vp] * 7 + [u32] + [vp] * 10,
     "lz_timing_create": [u32, C.POINTER(vp)],

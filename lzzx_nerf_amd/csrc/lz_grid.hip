@@ -24,26 +24,7 @@
 #include <math.h>
 #include <type_traits>
 
-#include "lz_grid_common.h"
-
-template <typename T> struct LzElem;
-template <> struct LzElem<float> {
-    static __device__ __forceinline__ float ld(const float* p) { return *p; }
-    static __device__ __forceinline__ float acc(float r, float w, float g) { return lz_fmaf(w, g, r); }
-    static __device__ __forceinline__ float accd(float r, float w, float gr, float gl) { return lz_fmaf(w, gr - gl, r); }
-    static __device__ __forceinline__ float st(float v) { return v; }
-};
-template <> struct LzElem<__half> {
-    static __device__ __forceinline__ float rh(float v) { return __half2float(__float2half_rn(v)); }
-    static __device__ __forceinline__ float ld(const __half* p) { return __half2float(*p); }
-    // at::Half semantics: the f32 product is rounded to f32 FIRST, then to half.  The opaque asm keeps the compiler from
-    // selecting v_fma_mixlo_f16 for cvt(mul(cvt(g), w)), which rounds the exact product once and differs in ~2^-13 of cases.
-    static __device__ __forceinline__ float mul32(float a, float b) { float p = a * b; asm("" : "+v"(p)); return p; }
-    static __device__ __forceinline__ float sum32(float a, float b) { float p = a + b; asm("" : "+v"(p)); return p; }
-    static __device__ __forceinline__ float acc(float r, float w, float g) { return rh(sum32(r, rh(mul32(w, g)))); }
-    static __device__ __forceinline__ float accd(float r, float w, float gr, float gl) { return rh(sum32(r, rh(mul32(w, rh(sum32(gr, -gl)))))); }
-    static __device__ __forceinline__ __half st(float v) { return __float2half_rn(v); }
-};
+#include "lz_grid_interp.h"   // LzElem, LzVec, the per-level interpolation (shared with lz_ngp_frame.hip)
 
 template <typename T, uint32_t D, uint32_t C>
 __global__ void __launch_bounds__(256)
@@ -411,10 +392,6 @@ static void lz_grid_lds_launch(const float* inputs, const T* emb, const int* off
 //     [tile][level][sample in tile][C]          (tile = Tn samples; same bytes as the tile's final [sample][level][C])
 // and lz_k_grid_untile then transposes every tile in place through LDS (one workgroup owns one tile: load all, barrier,
 // store all).  The untile pass costs one read + one write of the output (~0.3 ms per GB), far less than it saves.
-template <typename T, uint32_t C> struct LzVec {
-    T v[C];
-};
-
 template <typename T, uint32_t D, uint32_t C>
 __global__ void __launch_bounds__(256)
 lz_k_grid_forward_lm(const float* __restrict__ inputs, const T* __restrict__ grid, const int* __restrict__ offsets,
@@ -482,10 +459,7 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
     const T* g = grid + (size_t)lvl.off0 * C;
     float x[D];
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        x[d] = inputs[(size_t)b * D + d];
-        if (bound > 0.0f) x[d] = (x[d] + bound) / (2.0f * bound);
-    }
+    for (uint32_t d = 0; d < D; d++) x[d] = lz_grid_unit(inputs[(size_t)b * D + d], bound);
     const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);   // result zeroed below when out of range
     uint32_t own[NC][WORDS], oth[NC][WORDS];
     uint32_t term[D][2];
@@ -500,20 +474,10 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
 #pragma unroll
         for (uint32_t k = 0; k < WORDS; k++) oth[h][k] = (uint32_t)__shfl_xor((int)own[h][k], 1, 64);
     if (xb != 0) return;
-    float res[C];
+    LzVec<T, C> cv[1u << D];
 #pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) res[ch] = 0.0f;
-#pragma unroll
-    for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        const float wc = lz_grid_weight<D>(cell, idx);
-        LzVec<T, C> cvv;
-        __builtin_memcpy(&cvv, (idx & 1u) ? oth[idx >> 1] : own[idx >> 1], sizeof(T) * C);
-#pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) res[ch] = LzElem<T>::acc(res[ch], wc, LzElem<T>::ld(&cvv.v[ch]));
-    }
-    LzVec<T, C> o;
-#pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) o.v[ch] = LzElem<T>::st(cell.oob ? 0.0f : res[ch]);
+    for (uint32_t idx = 0; idx < (1u << D); idx++) __builtin_memcpy(&cv[idx], (idx & 1u) ? oth[idx >> 1] : own[idx >> 1], sizeof(T) * C);
+    const LzVec<T, C> o = lz_grid_interp<T, D, C>(cell, cv);
     T* out = outputs + ((size_t)b0 * L + (size_t)level * n + t) * C;
     __builtin_memcpy(__builtin_assume_aligned(out, sizeof(T) * C), &o, sizeof(T) * C);
 }

@@ -14,11 +14,17 @@
 //     lz_loop_composite_plain  accumulate, kill, count survivors
 // four launches per iteration of the reference's loop, enqueued back to back by lz_ngp_loop_run with the loop state in device memory.
 //
+// The 16 % above is a stand-alone gather.  The WHOLE frame as a persistent kernel was built and measured since (lz_ngp_frame.hip,
+// HashgridRenderer(mode = "fused")): with three waves per SIMD, 32 corner loads in flight per lane and the march, the matrix
+// chain and the compositing of other waves under the misses, the 256^2 x 128-step frame takes 1.07 ms against this loop's 3.14 under the
+// reference's schedule (1, 8) and 1.98 under (8, 8) (f32; f16 head 0.73 against 2.54 / 1.75), and 0.30 against 0.62 ms at max_steps 16.
+// The loop wins only on a 64^2 tile with the f16 head under the fat schedule (0.48 against 0.59 ms).  It stays the default mode.
+//
 // Arithmetic: every Linear is an fma chain in MFMA k order (oracle/ngp.py spells the order per layer); the first layer's k order follows
 // the tiled layout (lane q of a sample reads levels q, q + 4, q + 8, q + 12, both channels: one 8-byte load each), the hidden layers
 // consume the previous accumulator tile in place ("chained" order, as lz_head.hip).
 #include "lz_ngp_chain.h"       // fragment layout, the feature load and the f32 chain of lz_k_ngp_head (shared with lz_ngp_train.hip)
-#include "lz_head_f16w_slice.h"   // lz_k_ngp_head16: the 32x32x16 f16 operand layout, w_pack / w_zero, h_cvt2 / h_round
+#include "lz_ngp16_chain.h"     // lz_k_ngp_head16: the f16 chain on v_mfma_f32_32x32x16_f16 (shared with lz_ngp_frame.hip)
 #include <hip/hip_fp16.h>
 
 #ifndef LZN_WG_PER_CU
@@ -125,13 +131,6 @@ extern "C" int lz_ngp_head_forward(const float* packed, const void* feats, int f
 // that the four transcendentals of a sample sit two per lane: sigma_net output 0 (sigma) at tile row 4 and output 4 at row 0; colour
 // channels 0 / 1 / 2 at tile rows 0 / 4 / 1.  Lane half 0 then holds channel 0 (register 0) and channel 2 (register 1), lane half 1
 // channel 1 (register 0) and the sigma pre-activation (sigma_net.1's register 0).
-#define LZN16_S1 0     // fragment bases (fragment (ks, ft) at base + ks * NT + ft; 64 lanes x 8 halves each)
-#define LZN16_S2 4
-#define LZN16_C1 8
-#define LZN16_C2 12
-#define LZN16_FRAGS 16
-static_assert(LZN16_FRAGS * 64 * 16 == LZ_NGP_PACKED_F16_BYTES, "half image size mismatch with the header");
-
 struct LzNgp16K {
     const lz_h8* packed;
     const uint32_t* feats;  // tiled f16 features, one half2 (both channels of a level) per word
@@ -141,16 +140,6 @@ struct LzNgp16K {
     float* rgbs;
     uint32_t rows;
 };
-
-template <int KS, int NT>
-__device__ __forceinline__ void lzn16_layer(const lz_h8* __restrict__ frags, int lane, const lz_h8 (&b)[KS], lz_f16v (&acc)[NT]) {
-#pragma unroll
-    for (int ft = 0; ft < NT; ft++) acc[ft] = w_zero();
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++)
-#pragma unroll
-        for (int ft = 0; ft < NT; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(frags[(ks * NT + ft) * 64 + lane], b[ks], acc[ft], 0, 0, 0);
-}
 
 __global__ void __launch_bounds__(LZN_WG) lz_k_ngp_head16(LzNgp16K P) {
     __shared__ lz_h8 wl[LZN16_FRAGS * 64];
@@ -185,40 +174,15 @@ __global__ void __launch_bounds__(LZN_WG) lz_k_ngp_head16(LzNgp16K P) {
     for (; slice < n_slices; slice += stride) {
         const In cur = nxt;     // the next pass's loads are in flight under this pass's 16 MFMAs
         if (slice + stride < n_slices) load(slice + stride, nxt);
-        // ---------------- sigma_net: 32 -> 64 (ReLU) -> 16 ----------------
-        lz_h8 b1[2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++) {
-            const lz_u4v w = {cur.f[4 * ks], cur.f[4 * ks + 1], cur.f[4 * ks + 2], cur.f[4 * ks + 3]};
-            b1[ks] = __builtin_bit_cast(lz_h8, w);
-        }
-        lz_f16v s1[2];
-        lzn16_layer<2, 2>(wl + LZN16_S1 * 64, lane, b1, s1);
-        const lz_h8 b2[4] = {w_pack(s1[0], 0, true), w_pack(s1[0], 1, true), w_pack(s1[1], 0, true), w_pack(s1[1], 1, true)};
-        lz_f16v s2[1];
-        lzn16_layer<4, 1>(wl + LZN16_S2 * 64, lane, b2, s2);
-        // ---------------- colour_net: [SH(4) | sigma_net's 16 outputs, sigma's weighted 0] -> 64 (ReLU) -> 3 ----------------
-        lz_h8 c1in[2];
+        // SH(4) of the sample's direction as the packed halves of this lane half (components 8 h .. 8 h + 7), then the 16-MFMA chain
+        uint32_t shw[4];
         {
             float sh[16];
             lz_sh_eval(cur.dx, cur.dy, cur.dz, 4, sh, nullptr, nullptr, nullptr);
-            const lz_u4v w = {h_cvt2(h ? sh[8] : sh[0], h ? sh[9] : sh[1], false), h_cvt2(h ? sh[10] : sh[2], h ? sh[11] : sh[3], false),
-                              h_cvt2(h ? sh[12] : sh[4], h ? sh[13] : sh[5], false), h_cvt2(h ? sh[14] : sh[6], h ? sh[15] : sh[7], false)};
-            c1in[0] = __builtin_bit_cast(lz_h8, w);
+            lzn16_sh_words(sh, h, shw);
         }
-        c1in[1] = w_pack(s2[0], 0, false);
-        lz_f16v c1[2];
-        lzn16_layer<2, 2>(wl + LZN16_C1 * 64, lane, c1in, c1);
-        const lz_h8 c2in[4] = {w_pack(c1[0], 0, true), w_pack(c1[0], 1, true), w_pack(c1[1], 0, true), w_pack(c1[1], 1, true)};
-        lz_f16v c2[1];
-        lzn16_layer<4, 1>(wl + LZN16_C2 * 64, lane, c2in, c2);
-        // ---------------- two transcendentals per lane, one instruction sequence each ----------------
-        // chain A: colour channel h (register 0).  chain B: channel 2 (register 1) on h = 0, sigma on h = 1.  sigmoid(x) = 1 / (1 + exp(-x))
-        // is lz_sigmoidf's own sequence, so both chains are lz_expf / lz_sigmoidf bit for bit.
-        const float pa = (float)h_round(c2[0][0]);
-        const float pb = h ? (float)h_round(s2[0][0]) : (float)h_round(c2[0][1]);
-        const float ea = lz_expf(-pa), eb = lz_expf(h ? pb : -pb);
-        const float rgb_a = (float)h_round(1.0f / (1.0f + ea)), b_out = h ? eb : (float)h_round(1.0f / (1.0f + eb));
+        float rgb_a, b_out;
+        lzn16_chain(wl, lane, h, cur.f, shw, rgb_a, b_out);
         if (cur.valid) {
             float* rgb = P.rgbs + (size_t)cur.row * 3;
             rgb[h] = rgb_a;

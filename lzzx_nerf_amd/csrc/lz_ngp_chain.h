@@ -74,9 +74,10 @@ struct LznOut {
 
 // T slices per pass: every A fragment is read from LDS once and feeds T MFMAs, and the T accumulation chains interleave (the 16-deep
 // chains of the two 64 -> N layers are dependent MFMAs otherwise); wl: the LZ_NGP_FRAGS fragments
+// The chain in two halves, so that a caller whose SH components are a per-ray constant (lz_ngp_frame.hip keeps them in its ray slots)
+// supplies o.shq itself between them; lzn_chain below is both with lz_sh_eval of the sample's direction in between.
 template <int T>
-__device__ __forceinline__ void lzn_chain(const float* __restrict__ wl, int lane, int q, const LznIn<T>& in, LznOut<T>& o) {
-    const float (&b1)[T][8] = in.b1;
+__device__ __forceinline__ void lzn_chain_sigma(const float* __restrict__ wl, int lane, const float (&b1)[T][8], LznOut<T>& o) {
     // ---------------- sigma_net: 32 -> 64 (ReLU) -> 16 ----------------
     {
         lz_f4 acc[T][4];
@@ -107,15 +108,12 @@ __device__ __forceinline__ void lzn_chain(const float* __restrict__ wl, int lane
 #pragma unroll
         for (int u = 0; u < T; u++) o.h[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, o.h1[u][ks], o.h[u], 0, 0, 0);
     }
+}
+// colour_net on o.shq (this lane's SH components 4 ks + q) and sigma_net's o.h
+template <int T>
+__device__ __forceinline__ void lzn_chain_colour(const float* __restrict__ wl, int lane, LznOut<T>& o) {
     // ---------------- colour_net: [SH(4) of the direction | geometry] -> 64 (ReLU) -> 3 ----------------
     {
-#pragma unroll
-        for (int u = 0; u < T; u++) {
-            float sh[16];
-            lz_sh_eval(in.dx[u], in.dy[u], in.dz[u], 4, sh, nullptr, nullptr, nullptr);
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) o.shq[u][ks] = q == 0 ? sh[4 * ks] : (q == 1 ? sh[4 * ks + 1] : (q == 2 ? sh[4 * ks + 2] : sh[4 * ks + 3]));
-        }
         lz_f4 acc[T][4];
 #pragma unroll
         for (int u = 0; u < T; u++)
@@ -145,5 +143,17 @@ __device__ __forceinline__ void lzn_chain(const float* __restrict__ wl, int lane
 #pragma unroll
         for (int u = 0; u < T; u++) o.c[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, o.c1[u][ks], o.c[u], 0, 0, 0);
     }
+}
+template <int T>
+__device__ __forceinline__ void lzn_chain(const float* __restrict__ wl, int lane, int q, const LznIn<T>& in, LznOut<T>& o) {
+    lzn_chain_sigma<T>(wl, lane, in.b1, o);
+#pragma unroll
+    for (int u = 0; u < T; u++) {
+        float sh[16];
+        lz_sh_eval(in.dx[u], in.dy[u], in.dz[u], 4, sh, nullptr, nullptr, nullptr);
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) o.shq[u][ks] = q == 0 ? sh[4 * ks] : (q == 1 ? sh[4 * ks + 1] : (q == 2 ? sh[4 * ks + 2] : sh[4 * ks + 3]));
+    }
+    lzn_chain_colour<T>(wl, lane, o);
 }
 #endif

@@ -162,6 +162,12 @@ class FusedHashgridTrainNeRF(nn.Module):
                     table_grad=self.table_grad)
         return _NgpTrain.apply(meta, xyzs, dirs, emb.contiguous(), *[w.contiguous() for w in ws])
 
-    def to_inference(self, precision="f32"):
-        """an `ngp.FusedHashgridNeRF` on the current weights (renders through `ngp.HashgridRenderer`); its table is the live parameter"""
-        return FusedHashgridNeRF(self.encoder, self.sigma_net, self.color_net, precision=precision)
+    def to_inference(self, precision="f32", mode=None, **renderer):
+        """an `ngp.FusedHashgridNeRF` on the current weights (renders through `ngp.HashgridRenderer`); its table is the live parameter.
+        With `mode` ("loop" / "fused") or renderer arguments (density_bitfield=..., bound=..., cap=...): the `ngp.HashgridRenderer` of that
+        network in that mode instead."""
+        net = FusedHashgridNeRF(self.encoder, self.sigma_net, self.color_net, precision=precision)
+        if mode is None and not renderer:
+            return net
+        from .ngp import HashgridRenderer
+        return HashgridRenderer(net, mode="loop" if mode is None else mode, **renderer)
