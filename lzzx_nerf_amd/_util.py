@@ -49,5 +49,14 @@ def as_f32(t):
     return None if t is None else t.float().contiguous()
 
 
+def map01(x, bound):
+    """[-bound, bound] -> [0, 1], GridEncoder.forward's first line (grid.py:143), for a tensor `x` and a Python number `bound`: THE mapping on
+    the Python side.  The expression is the reference's own and stays differentiable; on the device torch evaluates a division by a
+    host scalar as the add followed by a multiplication with the scalar's f32 reciprocal (measured:
+    tests/test_gpu_bound_mapping.py::test_device_division_by_scalar_is_a_reciprocal_multiply), which csrc/lz_common.h: lz_map01 and
+    oracle.oracle.map01 restate.  Never divide by a tensor here: that is a true division, other bits when 2 bound is no power of two."""
+    return (x + bound) / (2 * bound)
+
+
 def call(name, *args):
     _lib.call(name, *args)

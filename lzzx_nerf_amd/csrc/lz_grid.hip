@@ -444,9 +444,10 @@ template <typename T, uint32_t D, uint32_t C>
 __global__ void __launch_bounds__(512)
 lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ grid, const int* __restrict__ offsets,
                       T* __restrict__ outputs, uint32_t B, uint32_t L, LzGridLevels lv, uint32_t gridtype, bool align_corners,
-                      const int* __restrict__ count = nullptr, float bound = 0.0f) {
+                      const int* __restrict__ count = nullptr, float bound = 0.0f, float inv2b = 0.0f) {
     // count (lz_grid_encode_forward_tiled): rows that hold samples this launch, read on the device (the render loop's n_alive * n_step); tiles
-    // behind it do nothing.  bound > 0: inputs arrive in [-bound, bound] and are mapped like GridEncoder.forward, (x + bound) / (2 bound) (grid.py:143)
+    // behind it do nothing.  bound > 0: inputs arrive in [-bound, bound] and are mapped like GridEncoder.forward (grid.py:143) by lz_map01 with
+    // inv2b = 1.0f / (2 bound), which the host forms
     constexpr uint32_t NC = 1u << (D - 1), WORDS = sizeof(T) * C / 4;
     static_assert(sizeof(T) * C % 4 == 0, "pair kernel moves whole dwords");
     const uint32_t Tn = blockDim.x >> 1, tile = blockIdx.x, level = blockIdx.y, t = threadIdx.x >> 1, xb = threadIdx.x & 1u;
@@ -459,7 +460,7 @@ lz_k_grid_forward_lmp(const float* __restrict__ inputs, const T* __restrict__ gr
     const T* g = grid + (size_t)lvl.off0 * C;
     float x[D];
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) x[d] = lz_grid_unit(inputs[(size_t)b * D + d], bound);
+    for (uint32_t d = 0; d < D; d++) x[d] = lz_grid_unit(inputs[(size_t)b * D + d], bound, inv2b);
     const LzGridCell<D> cell = lz_grid_cell<D, true>(x, lvl.scale, align_corners);   // result zeroed below when out of range
     uint32_t own[NC][WORDS], oth[NC][WORDS];
     uint32_t term[D][2];
@@ -906,10 +907,10 @@ extern "C" int lz_grid_encode_forward_tiled(const float* inputs, const void* emb
     hipStream_t st = lz_st(stream);
     if (emb_f16)
         hipLaunchKernelGGL((lz_k_grid_forward_lmp<__half, 3, 2>), dim3(tiles, L), dim3(2 * Tn), 0, st, inputs, (const __half*)embeddings, offsets,
-                           (__half*)outputs, B, L, lv, gridtype, ac, count, bound);
+                           (__half*)outputs, B, L, lv, gridtype, ac, count, bound, bound > 0.0f ? 1.0f / (2.0f * bound) : 0.0f);
     else
         hipLaunchKernelGGL((lz_k_grid_forward_lmp<float, 3, 2>), dim3(tiles, L), dim3(2 * Tn), 0, st, inputs, (const float*)embeddings, offsets,
-                           (float*)outputs, B, L, lv, gridtype, ac, count, bound);
+                           (float*)outputs, B, L, lv, gridtype, ac, count, bound, bound > 0.0f ? 1.0f / (2.0f * bound) : 0.0f);
     LZ_CHECK_LAUNCH("grid_encode_forward_tiled");
     return LZ_OK;
 }

@@ -30,11 +30,9 @@ template <typename T, uint32_t C> struct LzVec {
     T v[C];
 };
 
-// bound > 0: x arrives in [-bound, bound] and is mapped like GridEncoder.forward, (x + bound) / (2 bound) (grid.py:143); 0: already in [0, 1]
-__device__ __forceinline__ float lz_grid_unit(float x, float bound) {
-    if (bound > 0.0f) x = (x + bound) / (2.0f * bound);
-    return x;
-}
+// bound > 0: x arrives in [-bound, bound] and is mapped like GridEncoder.forward (grid.py:143; lz_map01, lz_common.h); 0: already in [0, 1].
+// inv2b = 1.0f / (2.0f * bound): formed once per thread by the caller, outside its loops (unused when bound is 0)
+__device__ __forceinline__ float lz_grid_unit(float x, float bound, float inv2b) { return bound > 0.0f ? lz_map01(x, bound, inv2b) : x; }
 
 // element offsets (index * C) of the 2^D corners of `cell` in the level's table, corner idx = bit d set: upper corner in dimension d
 template <uint32_t D>

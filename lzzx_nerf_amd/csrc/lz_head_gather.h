@@ -90,17 +90,20 @@ typedef float lz_gf2 __attribute__((ext_vector_type(2)));
 // (x + bound) / (2 bound) of a sample, grid.py:143 -- what lz_head_gather starts with; a caller that gathers one sample in several calls
 // (the 32-sample f16 slice) maps it once and passes MAPPED = true
 __device__ __forceinline__ void lz_head_map01(float px, float py, float pz, float bound, float two_bound, float (&c01)[3]) {
-    // When 2 bound is a power of two (bound 1, 2, 4 ...: every scene of the reference) the division equals the multiplication by its exact
-    // reciprocal bit for bit, and an IEEE division is ~11 VALU instructions (readfirstlane: `two_bound` reaches this point in a vector
-    // register, and a condition computed from it counts as divergent -- the compiler then evaluates BOTH sides below, three IEEE division
-    // sequences of ~10 instructions each per slice, and selects; as a scalar it is a branch)
+    // The mapping is lz_map01 (lz_common.h): the add, then a multiplication by the f32 reciprocal of 2 bound -- what torch computes on the
+    // device for the reference's division by a host scalar.  When 2 bound is a power of two (bound 1, 2, 4 ...: the reference's default
+    // scenes; its --bound is a float) that reciprocal is exact and comes from the exponent bits; otherwise it costs one IEEE division,
+    // ~11 VALU instructions, per call (readfirstlane: `two_bound` reaches this point in a vector register, and a condition computed from
+    // it counts as divergent -- the compiler then evaluates BOTH sides below and selects; as a scalar it is a branch)
     const uint32_t tb_bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(two_bound));
     const bool pow2 = (tb_bits & 0x007fffffu) == 0u && tb_bits > 0x00800000u && tb_bits < 0x7f000000u;   // wave-uniform
     if (pow2) {
         const float inv = __uint_as_float(0x7f000000u - tb_bits);    // 2^-k for two_bound = 2^k
         c01[0] = (px + bound) * inv; c01[1] = (py + bound) * inv; c01[2] = (pz + bound) * inv;
     } else {
-        c01[0] = (px + bound) / two_bound; c01[1] = (py + bound) / two_bound; c01[2] = (pz + bound) / two_bound;
+        // the division runs on the wave-uniform copy and its quotient goes back to a scalar register: no vector register stays live for it
+        const float inv2b = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(1.0f / __uint_as_float(tb_bits))));
+        c01[0] = lz_map01(px, bound, inv2b); c01[1] = lz_map01(py, bound, inv2b); c01[2] = lz_map01(pz, bound, inv2b);
     }
 }
 

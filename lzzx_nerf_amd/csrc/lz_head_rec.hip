@@ -953,20 +953,11 @@ lz_k_triplane_head_backward_rec(LzHeadBwdArgs A, const float* __restrict__ st, u
 // ------------------------------------------------------------------------------------------------
 // plane coordinates of the three table scatters: [3][M][2] = ((x, y) | (y, z) | (x, z)) mapped like the forward (lz_head_gather.h)
 // ------------------------------------------------------------------------------------------------
-__global__ void lz_k_plane_coords(const float* __restrict__ xyzs, uint32_t M, float bound, float* __restrict__ out) {
+__global__ void lz_k_plane_coords(const float* __restrict__ xyzs, uint32_t M, float bound, float inv2b, float* __restrict__ out) {
     const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= M) return;
-    const float two_bound = 2.0f * bound;
-    const uint32_t tb_bits = __float_as_uint(two_bound);
-    const bool pow2 = (tb_bits & 0x007fffffu) == 0u && tb_bits > 0x00800000u && tb_bits < 0x7f000000u;
     const float px = xyzs[(size_t)m * 3], py = xyzs[(size_t)m * 3 + 1], pz = xyzs[(size_t)m * 3 + 2];
-    float x01, y01, z01;
-    if (pow2) {
-        const float inv = __uint_as_float(0x7f000000u - tb_bits);
-        x01 = (px + bound) * inv; y01 = (py + bound) * inv; z01 = (pz + bound) * inv;
-    } else {
-        x01 = (px + bound) / two_bound; y01 = (py + bound) / two_bound; z01 = (pz + bound) / two_bound;
-    }
+    const float x01 = lz_map01(px, bound, inv2b), y01 = lz_map01(py, bound, inv2b), z01 = lz_map01(pz, bound, inv2b);
     float2* o = reinterpret_cast<float2*>(out);
     o[m] = make_float2(x01, y01);
     o[(size_t)M + m] = make_float2(y01, z01);
@@ -977,7 +968,7 @@ extern "C" int lz_triplane_plane_coords(const float* xyzs, uint32_t M, float bou
     LZ_REQUIRE(M == 0 || (xyzs && out), LZ_ERR_BAD_ARGUMENT, "triplane_plane_coords: null tensor");
     LZ_REQUIRE(((uintptr_t)out & 7u) == 0, LZ_ERR_BAD_ARGUMENT, "triplane_plane_coords: out must be 8-byte aligned");
     if (M == 0) return LZ_OK;
-    hipLaunchKernelGGL(lz_k_plane_coords, dim3(lz_div_up(M, 256)), dim3(256), 0, lz_st(stream), xyzs, M, bound, out);
+    hipLaunchKernelGGL(lz_k_plane_coords, dim3(lz_div_up(M, 256)), dim3(256), 0, lz_st(stream), xyzs, M, bound, 1.0f / (2.0f * bound), out);
     LZ_CHECK_LAUNCH("triplane_plane_coords");
     return LZ_OK;
 }

@@ -45,6 +45,7 @@ struct LzNgpFrameArgs {
     const void* emb;             // hash table, f32 or half [offsets[16], 2]
     const int* offsets;          // [17]
     LzGridLevels lv;
+    float inv2b;                 // 1.0f / (2 bound): lz_map01's factor
 };
 
 // slot state in LDS, per wave [field][NS]
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(LZNF_WG) lz_k_ngp_frame(LzNgpFrameArgs P, LzFr
         if constexpr (PREC == 0) {
             const int s = lane & 15, q = lane >> 4;
             // (slots without a sample carry the position 0: in range, its loads are harmless and its columns are dropped)
-            const float xin[3] = {lz_grid_unit(__shfl(x, s, 64), F.bound), lz_grid_unit(__shfl(y, s, 64), F.bound), lz_grid_unit(__shfl(z, s, 64), F.bound)};
+            const float xin[3] = {lz_grid_unit(__shfl(x, s, 64), F.bound, P.inv2b), lz_grid_unit(__shfl(y, s, 64), F.bound, P.inv2b), lz_grid_unit(__shfl(z, s, 64), F.bound, P.inv2b)};
             LzGridCell<3> cell[4];
             LzVec<TT, 2> cv[4][8];
 #pragma unroll
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(LZNF_WG) lz_k_ngp_frame(LzNgpFrameArgs P, LzFr
             }
         } else {
             const int s = lane & 31, h = lane >> 5;
-            const float xin[3] = {lz_grid_unit(__shfl(x, s, 64), F.bound), lz_grid_unit(__shfl(y, s, 64), F.bound), lz_grid_unit(__shfl(z, s, 64), F.bound)};
+            const float xin[3] = {lz_grid_unit(__shfl(x, s, 64), F.bound, P.inv2b), lz_grid_unit(__shfl(y, s, 64), F.bound, P.inv2b), lz_grid_unit(__shfl(z, s, 64), F.bound, P.inv2b)};
             uint32_t fw[8];
 #pragma unroll
             for (int ks = 0; ks < 2; ks++) {                         // levels 8 ks + 4 h + i: 32 four-byte corner loads in flight per k-step
@@ -376,6 +377,7 @@ extern "C" int lz_ngp_frame_render(const lz_frame_ngp_fused* f, lz_timing* timin
     a.packed = f->precision == 1 ? f->packed16 : static_cast<const void*>(f->packed);
     a.emb = f->embeddings;
     a.offsets = f->offsets;
+    a.inv2b = 1.0f / (2.0f * f->bound);
     LZ_REQUIRE(lz_fill_levels(a.lv, f->enc_L, f->enc_S, f->enc_H) == 0, LZ_ERR_UNSUPPORTED, "ngp_frame_render: at most %d levels", LZ_MAX_LEVELS);
     LzFrameK K;
     memset(&K, 0, sizeof(K));

@@ -32,9 +32,8 @@ struct LzTriGrads {
     float* t[3];
 };
 
-// (x + bound) / (2 bound) as GridEncoder.forward evaluates it on the device (grid.py:143): torch adds the scalar in f32, then multiplies
-// by the f32 reciprocal of the scalar divisor -- two roundings.  inv2b = 1.0f / (2 bound), formed on the host.
-__device__ __forceinline__ float lz_tri_map01(float v, float bound, float inv2b) { return (v + bound) * inv2b; }
+// (x + bound) / (2 bound) is lz_map01 (lz_common.h): what GridEncoder.forward computes on the device, measured to be the add followed by a
+// multiplication with inv2b = 1.0f / (2 bound), which the host forms.
 
 // The plane's two coordinates: xy = (x, y), yz = (y, z), xz = (x, z) (network.py:210-212)
 __device__ __forceinline__ constexpr uint32_t lz_tri_d0(uint32_t plane) { return plane == 1u ? 1u : 0u; }
@@ -57,7 +56,7 @@ lz_k_triplane_encode(const float* __restrict__ xyz, LzTriTables emb, const int* 
 #pragma unroll
         for (uint32_t d = 0; d < 3; d++) {
             const float v = lane < n ? xyz[(size_t)b * 3 + d] : 0.0f;   // idle lanes of the last wave gather at the centre and store nothing
-            c01[d] = lz_tri_map01(v, bound, inv2b);
+            c01[d] = lz_map01(v, bound, inv2b);
             oobc[d] = c01[d] < 0 || c01[d] > 1;
         }
 #pragma unroll 2
@@ -138,7 +137,7 @@ lz_k_triplane_encode(const float* __restrict__ xyz, LzTriTables emb, const int* 
 template <typename Add>
 __device__ __forceinline__ void lz_tri_sample_terms(const float* __restrict__ xyz, uint32_t b, uint32_t d0, uint32_t d1, float bound,
                                                     float inv2b, const LzGridLevel& lvl, float g, Add&& add) {
-    const float x[2] = {lz_tri_map01(xyz[(size_t)b * 3 + d0], bound, inv2b), lz_tri_map01(xyz[(size_t)b * 3 + d1], bound, inv2b)};
+    const float x[2] = {lz_map01(xyz[(size_t)b * 3 + d0], bound, inv2b), lz_map01(xyz[(size_t)b * 3 + d1], bound, inv2b)};
     const LzGridCell<2> cell = lz_grid_cell<2, false>(x, lvl.scale, false);
     if (cell.oob) return;
     uint32_t term[2][2];

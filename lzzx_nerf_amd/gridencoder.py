@@ -11,7 +11,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
-from ._util import call, ptr, require_cuda, stream, workspace
+from ._util import call, map01, ptr, require_cuda, stream, workspace
 
 _gridtype_to_id = {"hash": 0, "tiled": 1}
 
@@ -194,7 +194,7 @@ class GridEncoder(nn.Module):
         return "GridEncoder: " + self.extra_repr()
 
     def forward(self, inputs, bound=1):
-        unit = (inputs + bound) / (2 * bound)               # [-bound, bound] -> [0, 1] (grid.py:143)
+        unit = map01(inputs, bound)                         # [-bound, bound] -> [0, 1] (grid.py:143)
         rows = unit.view(-1, self.input_dim)
         feats = grid_encode(rows, self.embeddings, self.offsets, self.per_level_scale, self.base_resolution, rows.requires_grad,
                             self.gridtype_id, self.align_corners)
@@ -235,7 +235,7 @@ class _triplane_encode(Function):
         if ordered:
             # the checker's summation order per plane (lz_grid_encode_backward_ordered_strided); the plane's [0, 1] coordinates as the
             # three-encoder path forms them
-            unit = (xyz + bound) / (2 * bound)
+            unit = map01(xyz, bound)
             need = int(_lib.load().lz_grid_ordered_workspace(B, 2))
             nbytes = min(need, ORDERED_WORKSPACE_CAP)
             ws = workspace("grid_ordered", xyz.device, nbytes, grow=True)

@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib, gridencoder
-from ._util import as_f32, call, ptr, stream, workspace
+from ._util import as_f32, call, map01, ptr, stream, workspace
 from .encoding import get_encoder
 from .linear import MLP
 from .ngp import GEO, HIDDEN, FusedHashgridNeRF, _check_shapes, _fragment_tables
@@ -81,8 +81,8 @@ class _NgpTrain(Function):
             d_feats = torch.empty(16, M, 2, dtype=torch.float32, device=dev)
             call("lz_ngp_head_backward", ptr(packed), ptr(ws0), ptr(ws1), ptr(wc0), ptr(wc1), ptr(feats), ptr(dirs), M, None, ptr(g_sigma),
                  ptr(g_rgb), ptr(d_feats), *[ptr(g) for g in gws], ptr(_workspace(dev)), stream())
-            # the gather's own mapping, (x + bound) / (2 bound) in f32 (a true division: torch divides by a host scalar as a reciprocal multiply)
-            unit = (xyzs + meta["bound"]) / torch.full((1,), 2.0 * meta["bound"], dtype=torch.float32, device=dev)
+            # the gather's own mapping (lz_grid_unit -> lz_map01): torch's division by a host scalar, measured to be a reciprocal multiply
+            unit = map01(xyzs, meta["bound"])
             if (meta["table_grad"] or gridencoder.table_grad()) == "ordered":
                 gridencoder.grid_backward_ordered(d_feats, unit, emb, meta["offsets"], g_emb, M, 3, 2, 16, meta["S"], meta["H"], None, None, 0,
                                                   False, 0)

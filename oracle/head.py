@@ -58,7 +58,7 @@ class TriplaneSpec:
 
 def encode_plane(spec, uv, emb):
     """GridEncoder.forward, grid.py:139-154: map [-bound, bound] -> [0, 1], then grid_encode."""
-    x = (uv.astype(F32) + F32(spec.bound)) / F32(2 * spec.bound)
+    x = O.map01(uv, spec.bound)
     out, _ = O.grid_encode_forward(x, emb, spec.offsets, spec.per_level_scale, spec.base_resolution)
     return out
 

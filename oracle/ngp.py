@@ -42,7 +42,7 @@ def head_forward(W, feats, dirs):
 def network(W, emb, offsets, per_level_scale, base_resolution=16):
     """(xyzs, dirs, bound) -> (sigma, rgb): GridEncoder.forward (grid.py:139-154) + head_forward; a half table yields half features"""
     def net(xyzs, dirs, bound):
-        x01 = (np.asarray(xyzs, F32) + F32(bound)) / F32(2 * bound)
+        x01 = O.map01(xyzs, bound)
         feats, _ = O.grid_encode_forward(x01, emb, offsets, per_level_scale, base_resolution)
         return head_forward(W, feats.astype(F32), dirs)
     return net

@@ -106,6 +106,16 @@ def _i32(a):
 u32, f32c, i32c = C.c_uint32, C.c_float, C.c_int
 
 
+def map01(x, bound):
+    """[-bound, bound] -> [0, 1]: `(inputs + bound) / (2 * bound)`, gridencoder/grid.py:143, in the arithmetic torch runs it in ON THE DEVICE,
+    where the reference is deployed: the f32 add, then a multiplication by the f32 reciprocal of 2 bound (a tensor divided by a host
+    scalar; measured by tests/test_gpu_bound_mapping.py::test_device_division_by_scalar_is_a_reciprocal_multiply).  torch on the CPU
+    divides instead: the same bits when 2 bound is a power of two, other bits for a third of all coordinates at bound 1.5.  Every
+    checker that maps a position calls this; the kernels' counterpart is csrc/lz_common.h: lz_map01."""
+    b = np.float32(bound)
+    return (np.asarray(x, np.float32) + b) * (np.float32(1) / (np.float32(2) * b))
+
+
 # ----------------------------------------------------------------------------------------------
 # gridencoder
 # ----------------------------------------------------------------------------------------------

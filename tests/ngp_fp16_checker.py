@@ -24,7 +24,7 @@ LAYERS = ("sigma_net.net.0", "sigma_net.net.1", "color_net.net.0", "color_net.ne
 
 def features(emb, offsets, per_level_scale, xyz, bound, base_resolution=16):
     """GridEncoder.forward (grid.py:139-154) on a half copy of the table -> half features [M, 32]"""
-    x01 = (np.asarray(xyz, F32) + F32(bound)) / F32(2 * bound)
+    x01 = O.map01(xyz, bound)
     feats, _ = O.grid_encode_forward(x01, np.asarray(emb).astype(F16), offsets, per_level_scale, base_resolution)
     return feats
 

@@ -20,10 +20,10 @@ from oracle import oracle as O
 F32 = np.float32
 SQRT3F = F32(1.7320508075688772)
 
-REGIMES = ("behind", "side", "cascades", "var_dt", "inside", "aabb", "grid64", "grid512", "axis", "odd", "encoder")
+REGIMES = ("behind", "side", "cascades", "var_dt", "inside", "aabb", "grid64", "grid512", "axis", "odd", "encoder", "bound15")
 SMALL_ENCODER = dict(num_levels=16, level_dim=2, base_resolution=4, log2_hashmap_size=12, desired_resolution=512)
 
-N_RUNS = {"cascades": 2, "inside": 2, "axis": 2}      # every other regime is one run
+N_RUNS = {"cascades": 2, "inside": 2, "axis": 2, "bound15": 2}      # every other regime is one run
 RUN_IDS = tuple((r, i) for r in REGIMES for i in range(N_RUNS.get(r, 1)))
 
 AXIS_O = np.array([(0, 0, -3), (0.1, 0.05, -3), (-3, 0, 0), (0, 3, 0), (0, 0, -3), (0.5, 0.5, -3), (0, 0, 3)], F32)
@@ -109,6 +109,11 @@ def _runs(regime):
         return (_run("odd", *_camera(H=37, W=41), "holes"),)
     if regime == "encoder":
         return (_run("encoder", *_camera(), "holes", encoder="small"),)
+    if regime == "bound15":
+        # 2 bound = 3 is no power of two: the box-to-unit mapping's reciprocal multiply and a true division differ here (tests/bound_cases.py)
+        # "two": no sample leaves the unit cube; "two_wide": its level-1 ellipsoid, at 1.5 times the size, reaches x = +-1.05 -- samples of
+        # the outer level, whose box is [-1.5, 1.5]^3
+        return tuple(_run("bound15-" + b, *_camera(orbit_pose(157)), b, bound=1.5, cascade=2) for b in ("two", "two_wide"))
     raise KeyError(regime)
 
 
@@ -315,6 +320,8 @@ def check_regime(regime, frames):
         assert dt_min > dt_max and f["steps"].size > 0 and (f["steps"] == dt_max).all()
     elif regime == "odd":
         assert int((run.rd[:, 0] == 0).sum()) >= 37
+    elif regime == "bound15":
+        assert int((frames[1]["reach"] > 1).sum()) >= 100          # samples in cascade 1, where the box is [-1.5, 1.5]^3
     elif regime == "axis":
         for g in frames:
             assert (g["nears"] == 2).all() and (g["fars"] == 4).all()

@@ -28,7 +28,7 @@ class _Cpu:
         self.W = {k: v.numpy() for k, v in W.items()}
 
     def net(self, xyzs, dirs, bound):
-        x01 = (xyzs + F32(bound)) / F32(2 * bound)
+        x01 = O.map01(xyzs, bound)
         h, _ = O.grid_encode_forward(x01, self.emb, self.offsets, self.pls, 16)
         h = O.linear(O.linear(h, self.W["s0"], relu=True), self.W["s1"])
         sigma = O.unary("exp", np.ascontiguousarray(h[:, 0]))

@@ -391,11 +391,21 @@ def test_fused_frame_two_cascades_with_occupancy_bounds(params, golden, precisio
     """bound = 2 (two cascade levels, renderer.py:93; tables sized for desired_resolution 512 * bound, network.py:131): the fused frame with
     the march confined to the occupied bounds of BOTH levels (a blob in the inner level, a larger one in the outer level only) against
     the unclipped kernel and the multi-launch loop -- mip_from_pos / mip_from_dt, per-level dilation and the union of the level boxes"""
+    _two_cascades_with_occupancy_bounds(params, golden, precision, 2.0)
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16"])
+def test_fused_frame_two_cascades_with_occupancy_bounds_at_bound_1p5(params, golden, precision):
+    """the same at bound 1.5 (level 1 spans [-1.5, 1.5]^3): 2 bound is no power of two, the head's mapping takes lz_head_map01's other branch.
+    f16: the only bit-for-bit comparison of the half slices' mapping at such a bound (frame kernel against the loop's f16 head)"""
+    _two_cascades_with_occupancy_bounds(params, golden, precision, 1.5)
+
+
+def _two_cascades_with_occupancy_bounds(params, golden, precision, bound):
     from lzzx_nerf_amd.gridencoder import GridEncoder
     from lzzx_nerf_amd.head import FusedTriplaneHead
     from lzzx_nerf_amd.renderer import TriplaneRenderer
     from lzzx_nerf_amd.utils import frame_rays
-    bound = 2.0
     enc = GridEncoder(input_dim=2, num_levels=12, level_dim=1, base_resolution=64, log2_hashmap_size=14, desired_resolution=512 * bound)
     g = torch.Generator().manual_seed(21)
     sd = {k: torch.from_numpy(v) for k, v in params.items()}
@@ -407,7 +417,7 @@ def test_fused_frame_two_cascades_with_occupancy_bounds(params, golden, precisio
     pose, intr = synthetic_camera(H, W)
     ro, rd = frame_rays(dev(pose), intr, H, W)
     cond = (dev(golden["net_enc_a"]), dev(golden["net_ind"]), dev(golden["net_eye"]))
-    # level 0 spans [-1, 1]^3, level 1 [-2, 2]^3: a blob around the origin in level 0 and a shell part only level 1 sees
+    # level 0 spans [-1, 1]^3, level 1 [-bound, bound]^3: a blob around the origin in level 0 and a shell part only level 1 sees
     cells = _blob(0, (64, 64, 64), 14) + _blob(1, (64, 64, 64), 9) + _blob(1, (80, 64, 100), 6)
     bits = _bitfield_from_cells(cells, 128, 2)
     aabb = torch.tensor([-bound, -bound / 2, -bound, bound, bound / 2, bound], device="cuda")

@@ -270,21 +270,21 @@ def _points(M, seed):
     return xyzs, dirs, torch.randn(M, generator=gen).cuda(), torch.randn(M, 3, generator=gen).cuda()
 
 
-def _table_grad_of(net, xyzs, dirs, gs, gr):
+def _table_grad_of(net, xyzs, dirs, gs, gr, bound=1.0):
     for p in net.parameters():
         p.grad = None
-    sigma, rgb = net(xyzs, dirs, 1.0)
+    sigma, rgb = net(xyzs, dirs, bound)
     torch.autograd.backward([sigma, rgb], [gs, gr])
     return net.encoder.embeddings.grad.clone()
 
 
-def _d_feats(net, xyzs, dirs, gs, gr):
+def _d_feats(net, xyzs, dirs, gs, gr, bound=1.0):
     """lz_ngp_head_backward's d feats [16, M, 2] straight from the entry point"""
     M = xyzs.shape[0]
     ws = [w.detach().contiguous() for w in _weights(net)]
     e = net.encoder
     feats = torch.empty(M, 32, device="cuda")
-    call("lz_grid_encode_forward_tiled", ptr(xyzs), ptr(e.embeddings), ptr(e.offsets), ptr(feats), M, None, 1.0, 3, 2, 16, net._S, net._H, 0, 0, 0,
+    call("lz_grid_encode_forward_tiled", ptr(xyzs), ptr(e.embeddings), ptr(e.offsets), ptr(feats), M, None, bound, 3, 2, 16, net._S, net._H, 0, 0, 0,
          stream())
     d = torch.empty(16, M, 2, device="cuda")
     gw = [torch.empty_like(w) for w in ws]
@@ -295,19 +295,11 @@ def _d_feats(net, xyzs, dirs, gs, gr):
 
 @pytest.mark.parametrize("M", [1, 257, 4099])
 def test_fused_net_table_gradient_repeats_and_equals_the_checker(generic, M):
-    from oracle import oracle as O
     with pytest.raises(ValueError):
         FusedHashgridTrainNeRF(table_grad="sorted")
     net = _fused(generic)
     xyzs, dirs, gs, gr = _points(M, 40 + M)
-    a = _table_grad_of(net, xyzs, dirs, gs, gr)
-    b = _table_grad_of(net, xyzs, dirs, gs, gr)
-    assert np.array_equal(_bits(a), _bits(b))
-    d = _d_feats(net, xyzs, dirs, gs, gr).permute(1, 0, 2).reshape(M, 32).cpu().numpy()
-    unit = ((xyzs + 1.0) / torch.full((1,), 2.0, device="cuda")).cpu().numpy()
-    e = net.encoder
-    ref, _ = O.grid_encode_backward(d, unit, tuple(e.embeddings.shape), e.offsets.cpu().numpy(), e.per_level_scale, e.base_resolution)
-    assert np.array_equal(_bits(a), _bits(ref))
+    ref = _table_gradient_repeats_and_equals_the_checker(net, xyzs, dirs, gs, gr, 1.0)
     # the module switch is what table_grad=None follows
     follow = _fused(generic, None)
     prev = gridencoder.set_table_grad("ordered")
@@ -316,6 +308,29 @@ def test_fused_net_table_gradient_repeats_and_equals_the_checker(generic, M):
     finally:
         gridencoder.set_table_grad(prev)
     assert np.array_equal(_bits(c), _bits(ref))
+
+
+def _table_gradient_repeats_and_equals_the_checker(net, xyzs, dirs, gs, gr, bound):
+    from oracle import oracle as O
+    M = xyzs.shape[0]
+    a = _table_grad_of(net, xyzs, dirs, gs, gr, bound)
+    b = _table_grad_of(net, xyzs, dirs, gs, gr, bound)
+    assert np.array_equal(_bits(a), _bits(b))
+    d = _d_feats(net, xyzs, dirs, gs, gr, bound).permute(1, 0, 2).reshape(M, 32).cpu().numpy()
+    unit = O.map01(xyzs.cpu().numpy(), bound)
+    e = net.encoder
+    ref, _ = O.grid_encode_backward(d, unit, tuple(e.embeddings.shape), e.offsets.cpu().numpy(), e.per_level_scale, e.base_resolution)
+    assert np.array_equal(_bits(a), _bits(ref))
+    return ref
+
+
+def test_fused_net_table_gradient_repeats_and_equals_the_checker_at_bound_1p5(generic):
+    """2 bound = 3: the scatter's coordinates are the gather's (tests/bound_cases.py: rows whose cell differs under a true division)"""
+    import bound_cases as BC
+    M = 257
+    _, dirs, gs, gr = _points(M, 40 + M)
+    xyzs = torch.from_numpy(BC.points(1.5, M, "cfg2").copy()).cuda()
+    _table_gradient_repeats_and_equals_the_checker(_fused(generic), xyzs, dirs, gs, gr, 1.5)
 
 
 def _five_steps(generic, ro, rd, nears, fars, bits, target):

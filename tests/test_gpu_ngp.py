@@ -39,8 +39,8 @@ def test_tiled_gather_equals_the_row_major_encoder(M, half):
     tables), the (x + bound) / (2 bound) mapping included; rows behind a device-side count are not touched"""
     g, fused, _, _ = make(half=half)
     rng = np.random.default_rng(M)
-    # bound 2 with points up to 2.3: some fall outside -> zero features (gridencoder.cu:98-122).  (A power of two: torch's GPU division by a
-    # python scalar multiplies by the rounded reciprocal, the kernel and the checker divide -- the two agree when 1 / (2 bound) is exact.)
+    # bound 2 with points up to 2.3: some fall outside -> zero features (gridencoder.cu:98-122).  (Other bounds, where 1 / (2 bound) is not
+    # exact: tests/test_gpu_bound_mapping.py.)
     x = dev(rng.uniform(-2.3, 2.3, (M, 3)).astype(F32))
     want = g.enc(x, bound=2.0) if not half else None
     if half:

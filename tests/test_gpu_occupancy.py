@@ -23,7 +23,7 @@ def _params_for_bound(params, bound, rng):
     return p
 
 
-@pytest.mark.parametrize("bound,G,thresh", [(1.0, 32, 0.01), (2.0, 16, 0.01), (1.0, 16, 1e9)])
+@pytest.mark.parametrize("bound,G,thresh", [(1.0, 32, 0.01), (2.0, 16, 0.01), (1.0, 16, 1e9), (1.5, 16, 0.01)])
 def test_update_density_grid_matches_checker(params, golden, bound, G, thresh):
     from lzzx_nerf_amd.head import FusedTriplaneHead
     from lzzx_nerf_amd.occupancy import update_density_grid
