@@ -1318,17 +1318,27 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
     // EVERY row of the gradient buffers is written here (the reference's wrapper pre-fills them with zeros, raymarching.py:649-653 -- five
     // fill launches and 170 MB per cfg3 step): a ray's rows behind its early termination get zeros in the loop below, and the rows no ray
     // owns -- in front of the first ray's, behind the last kept ray's (alignment padding, rays dropped for lack of room) -- right here.
+    // The head [0, min(first offset, M)) -- a non-zero counter base -- is workgroup 0's, on its own: the first ray can be the last kept ray
+    // or a dropped one as well, and a lane carries one (zb, ze) range for those.  No trip at base 0, the training step's.
+    if (blockIdx.x == 0) {
+        const uint32_t first = (uint32_t)rays[1], head = first < M ? first : M;
+        for (size_t i = lane; i < head; i += 64) {
+            grad_sigmas[i] = 0.0f;
+            grad_rgbs[i * 3] = 0.0f; grad_rgbs[i * 3 + 1] = 0.0f; grad_rgbs[i * 3 + 2] = 0.0f;
+            if (NAMB > 0) grad_amb0[i] = 0.0f;
+            if (NAMB > 1) grad_amb1[i] = 0.0f;
+            if (UNC) grad_unc[i] = 0.0f;
+        }
+    }
     uint32_t zb = 0, ze = 0;
     if (n < N) {
         index = (uint32_t)rays[(size_t)n * 3];
         offset = (uint32_t)rays[(size_t)n * 3 + 1];
         ns = (uint32_t)rays[(size_t)n * 3 + 2];
         const bool dropped = offset + ns > M;
-        if (n == 0 && offset > 0) { zb = 0; ze = offset < M ? offset : M; }
         if (dropped) {              // the dropped rays are a suffix: the first of them clears everything from its offset on
             const bool prev_kept = n == 0 || (uint32_t)rays[(size_t)(n - 1) * 3 + 1] + (uint32_t)rays[(size_t)(n - 1) * 3 + 2] <= M;
-            if (n == 0) { zb = 0; ze = M; }
-            else if (prev_kept && offset < M) { zb = offset; ze = M; }
+            if (prev_kept && offset < M) { zb = offset; ze = M; }
         } else if (n == N - 1 && offset + ns < M) { zb = offset + ns; ze = M; }
         if (ns == 0 || dropped) ns = 0;
     }

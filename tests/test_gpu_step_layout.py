@@ -19,39 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+from composite_cases import group_size, step_rows  # noqa: F401  (the row map lives with the shared compositing cases)
 from conftest import make_params, synthetic_camera
 
 pytestmark = pytest.mark.gpu
 
 MAX_STEPS = 64
-
-
-def group_size():
-    from lzzx_nerf_amd import _lib
-    return int(_lib.load().lz_train_group_size())
-
-
-def step_rows(rays, M):
-    """ray-major row -> step-major row for every sample a ray owns: dict-free numpy restatement of the header's formula.
-    rays [N, 3] (id, ray-major offset, count) in processing order; returns (src, dst): sample k of rays[i] sits at ray-major row src and
-    step-major row dst (dropped rays own nothing)."""
-    rays = np.asarray(rays, np.int64)
-    src, dst = [], []
-    G = group_size()
-    for g0 in range(0, len(rays), G):
-        grp = rays[g0:g0 + G]
-        c = np.where(grp[:, 1] + grp[:, 2] <= M, grp[:, 2], 0)
-        if c.max(initial=0) == 0:
-            continue
-        gb = grp[0, 1]
-        alive = c[None, :] > np.arange(c.max())[:, None]                 # [k, j]
-        pos = np.cumsum(alive.reshape(-1)).reshape(alive.shape) - 1       # k-major running index
-        k, j = np.nonzero(alive)
-        dst.append(gb + pos[k, j])
-        src.append(grp[j, 1] + k)
-    if not src:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64)
-    return np.concatenate(src), np.concatenate(dst)
 
 
 def _scene(name, device):
@@ -307,48 +280,55 @@ def test_a_callers_order_must_be_a_permutation():
 
 @pytest.mark.parametrize("n_rays", [1, 63, 64, 65, 129, 1000])
 @pytest.mark.parametrize("perturb", [False, True])
-def test_ragged_groups_empty_rays_and_perturbed_starts(n_rays, perturb):
+def test_ragged_groups_empty_rays_and_perturbed_starts(n_rays, perturb, monkeypatch):
     """group edges and rays without a sample: fewer rays than a group, one ray more than a group, rays that miss the occupied cells
     (count 0 inside a group), perturbed start times (the same noise under both layouts: the generator is re-seeded) -- march rows and
-    the triplane compositing forward / backward against the ray-major operators"""
+    the triplane compositing forward / backward against the ray-major operators; once from a counter base of 0 and once from a base of
+    40 (unowned rows in front of the first ray), the step-major backward's gradient buffers poisoned with NaN both times: it writes
+    every row itself"""
     from lzzx_nerf_amd import raymarching as R
     dev = torch.device("cuda")
     bits = _scene("ellipsoid", dev)
     ro, rd = _rays(dev, n_rays, size=64, seed=n_rays)
-    torch.manual_seed(1234)
-    a = _march(ro, rd, bits, "ray", perturb=perturb)
-    torch.manual_seed(1234)
-    b = _march(ro, rd, bits, "step", perturb=perturb)
-    counts = a[3][:, 2].cpu().numpy()
-    if n_rays >= 63:
-        assert (counts == 0).any() and (counts > 0).any()          # the 64 x 64 frame of the ellipsoid scene has rays of both kinds
-    _check_march(a, b, a[0].shape[0], None)
-    M, N = a[0].shape[0], n_rays
-    if M == 0:
-        return
-    g = torch.Generator(device=dev).manual_seed(7)
-    rnd = lambda *s: torch.rand(*s, device=dev, generator=g)
-    sig, rgb, a0, a1, un = rnd(M) * 30, rnd(M, 3), rnd(M), rnd(M), rnd(M)
-    # the SAME per-sample values under both layouts: ray-major values -> step-major rows through the two rays tables
-    ra, rb = a[3].cpu().numpy(), b[3].cpu().numpy()
-    src_b, dst_b = step_rows(rb, M)                                   # processing-order ray-major row -> step row
-    srt = np.argsort(src_b, kind="stable")
-    ids = np.repeat(rb[:, 0], rb[:, 2])
-    kk = src_b[srt] - np.repeat(rb[:, 1], rb[:, 2])
-    rm = torch.from_numpy(ra[ids, 1] + kk).to(dev)                    # the sample's row in the ray-major buffers
-    st = torch.from_numpy(dst_b[srt]).to(dev)
-    perm = lambda x: torch.zeros_like(x).index_copy_(0, st, x[rm])
-    f_r = R._composite_train_fwd((2, 0, 1), sig, rgb, a0, a1, un, a[2].contiguous(), a[3], 1e-4, 0)
-    f_s = R._composite_train_fwd((2, 0, 1), perm(sig), perm(rgb), perm(a0), perm(a1), perm(un), b[2].contiguous(), b[3], 1e-4, 1)
-    for x, y in zip(f_r, f_s):
-        assert torch.equal(x, y)
-    gws, ga0, ga1, gu, gim = rnd(N), rnd(N), rnd(N), rnd(N), rnd(N, 3)
-    ws, a0s, a1s, us, dep, img = f_r
-    b_r = R._composite_train_bwd((2, 0, 1), gws, ga0, ga1, gu, gim, sig, rgb, a0, a1, un, a[2].contiguous(), a[3], ws, a0s, us, img, 1e-4, 0)
-    b_s = R._composite_train_bwd((2, 0, 1), gws, ga0, ga1, gu, gim, perm(sig), perm(rgb), perm(a0), perm(a1), perm(un), b[2].contiguous(), b[3], ws,
-                                 a0s, us, img, 1e-4, 1)
-    for x, y in zip(b_r, b_s):
-        assert torch.equal(perm(x), y)
+    for ctr0 in ((0, 0), (40, 0)):         # (a single ray's buffer has max_steps = 64 rows: base + count must fit)
+        torch.manual_seed(1234)
+        a = _march(ro, rd, bits, "ray", perturb=perturb, ctr0=ctr0)
+        torch.manual_seed(1234)
+        b = _march(ro, rd, bits, "step", perturb=perturb, ctr0=ctr0)
+        counts = a[3][:, 2].cpu().numpy()
+        if n_rays >= 63:
+            assert (counts == 0).any() and (counts > 0).any()          # the 64 x 64 frame of the ellipsoid scene has rays of both kinds
+        assert int(a[3][0, 1]) == int(b[3][0, 1]) == ctr0[0]
+        _check_march(a, b, a[0].shape[0], None)
+        M, N = a[0].shape[0], n_rays
+        if M == 0:
+            continue
+        g = torch.Generator(device=dev).manual_seed(7)
+        rnd = lambda *s: torch.rand(*s, device=dev, generator=g)
+        sig, rgb, a0, a1, un = rnd(M) * 30, rnd(M, 3), rnd(M), rnd(M), rnd(M)
+        # the SAME per-sample values under both layouts: ray-major values -> step-major rows through the two rays tables
+        ra, rb = a[3].cpu().numpy(), b[3].cpu().numpy()
+        src_b, dst_b = step_rows(rb, M)                                   # processing-order ray-major row -> step row
+        srt = np.argsort(src_b, kind="stable")
+        ids = np.repeat(rb[:, 0], rb[:, 2])
+        kk = src_b[srt] - np.repeat(rb[:, 1], rb[:, 2])
+        rm = torch.from_numpy(ra[ids, 1] + kk).to(dev)                    # the sample's row in the ray-major buffers
+        st = torch.from_numpy(dst_b[srt]).to(dev)
+        perm = lambda x: torch.zeros_like(x).index_copy_(0, st, x[rm])
+        f_r = R._composite_train_fwd((2, 0, 1), sig, rgb, a0, a1, un, a[2].contiguous(), a[3], 1e-4, 0)
+        f_s = R._composite_train_fwd((2, 0, 1), perm(sig), perm(rgb), perm(a0), perm(a1), perm(un), b[2].contiguous(), b[3], 1e-4, 1)
+        for x, y in zip(f_r, f_s):
+            assert torch.equal(x, y)
+        gws, ga0, ga1, gu, gim = rnd(N), rnd(N), rnd(N), rnd(N), rnd(N, 3)
+        ws, a0s, a1s, us, dep, img = f_r
+        b_r = R._composite_train_bwd((2, 0, 1), gws, ga0, ga1, gu, gim, sig, rgb, a0, a1, un, a[2].contiguous(), a[3], ws, a0s, us, img, 1e-4, 0)
+        args_s = (gws, ga0, ga1, gu, gim, perm(sig), perm(rgb), perm(a0), perm(a1), perm(un), b[2].contiguous(), b[3], ws, a0s, us, img, 1e-4, 1)
+        with monkeypatch.context() as mp:     # (the wrapper hands the step-major kernel torch.empty_like buffers)
+            mp.setattr(torch, "empty_like", lambda t, **kw: torch.full_like(t, float("nan")))
+            b_s = R._composite_train_bwd((2, 0, 1), *args_s)
+        for x, y in zip(b_r, b_s):
+            assert not torch.isnan(y).any()
+            assert torch.equal(perm(x), y)
 
 
 def test_camera_gradients_through_the_step_major_march():

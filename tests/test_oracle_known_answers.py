@@ -390,7 +390,16 @@ def test_composite_train_forward_and_backward():
         hm[s] -= 1e-4
         fd = (loss2(hp) - loss2(hm)) / 2e-4
         assert g2["grad_sigmas"][s] == pytest.approx(fd, abs=2e-3 + 2e-3 * abs(fd))
-    assert np.allclose(g2["grad_rgbs"].sum(), g2["grad_rgbs"].sum())  # finite
+    # colour, ambient and uncertainty gradients per element against the float64 autograd model (composite_cases.model64) on these inputs,
+    # with early termination (g) and without (g2); bars: the checker's measured distance from the model (composite_cases.BARS)
+    import composite_cases as C
+    up = dict(g_weights_sum=gws, g_image=gimg, g_unc_sum=gu, g_amb0_sum=np.ones(40, np.float32), g_amb1_sum=2 * np.ones(40, np.float32))
+    for s_, g_ in ((sig, g), (sig_small, g2)):
+        m = C.model64("triplane", C.case_from_arrays("known_answers", rays, M, s_, dl, rgb, a0, a1, unc, 1e-4, rng, upstream=up))
+        assert m["near"].sum() <= 1
+        for k, bar in (("grad_rgbs", "grad_rgbs"), ("grad_amb0", "grad_amb"), ("grad_amb1", "grad_amb"), ("grad_unc", "grad_unc")):
+            assert C.max_abs_diff(g_[k], m["grads"][k], m["near_row"]) <= C.BARS[bar], (k, C.max_abs_diff(g_[k], m["grads"][k], m["near_row"]))
+            assert np.abs(m["grads"][k]).max() > 0.1
     assert np.all(g["grad_amb0"][g["grad_rgbs"][:, 0] != 0] == 1.0) and np.all(np.isin(g["grad_amb1"], [0.0, 2.0]))
 
 
