@@ -97,6 +97,30 @@ int lz_grid_encode_backward_ordered_strided(const void* grad, uint32_t grad_row_
                                             uint32_t gridtype, int align_corners, void* workspace, uint32_t workspace_bytes_lo,
                                             uint32_t workspace_bytes_hi, lz_stream_t stream);
 
+/* The ORDER-FREE table gradient (csrc/lz_grid_fixed.hip).  Additive under ABI version 11.  Per level, with m = max |grad| over the level's
+ * whole gradient (out-of-range rows included, a NaN counts as inf):  m < 2^ex,  hb = max(2, ceil(log2(B 2^D))),
+ * e = clamp(51 - hb - ex, -100, 100);  every term t = fl32(w g) becomes the integer q(t) = rint((double)t 2^e), the integers of an entry are
+ * added as int64 (A_i; it cannot overflow), and grad_embeddings[i] += fl32((double)A_i 2^-e) for every entry with A_i != 0 -- one
+ * rounding, one f32 add onto what the buffer holds; entries with A_i == 0 are not written.  Integer addition is associative: the same
+ * bits on every call, under any permutation of the rows, in either grad_layout and for any launch geometry, and the bits of the CPU
+ * checker whenever every term and sum is exact.  Per entry |result - real sum| <= n_i 2^-(e+1) + 1/2 ulp (n_i terms).  A level with
+ * m == 0 writes nothing; a level whose m is not finite is scattered with float atomics as lz_grid_encode_backward does it (non-finite
+ * values arrive where they arrive there; that level's bits are not promised).
+ * Arguments as lz_grid_encode_backward_ordered, plus grad_row_stride: 0 = dense, otherwise (grad_layout 1 only, no grad_inputs) the
+ * elements between two rows of a wider sample-major matrix, a multiple of C and >= L * C, as lz_grid_encode_backward_ordered_strided.
+ * f32 tables only, D 2 or 3, C 1 or 2, B * 2^D < 2^31 (LZ_ERR_UNSUPPORTED otherwise).  workspace: device memory, 16-byte aligned, no
+ * initialisation (the call clears it), lz_grid_fixed_workspace(n_entries, C) bytes for a table of n_entries = offsets[L] entries: a
+ * 256-byte header and one int64 per table element (0 for a C it does not serve).  What the host can see is checked before any launch
+ * (null tensors, alignment, a workspace below lz_grid_fixed_workspace(8 L, C): LZ_ERR_BAD_ARGUMENT); offsets live on the device, so a
+ * level whose accumulators lie past the end of a workspace sized for fewer entries is found there: it adds nothing and its first
+ * gradient element is set to NaN.  dy_dx / grad_inputs as lz_grid_encode_backward_ordered.  B = 0 is LZ_OK without a launch. */
+size_t lz_grid_fixed_workspace(uint32_t n_entries, uint32_t C);
+int lz_grid_encode_backward_fixed(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
+                                  void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
+                                  const void* dy_dx, void* grad_inputs, uint32_t gridtype, int align_corners, int emb_f16,
+                                  int grad_layout, void* workspace, uint32_t workspace_bytes_lo, uint32_t workspace_bytes_hi,
+                                  uint32_t grad_row_stride, lz_stream_t stream);
+
 /* The triplane position encoder as one operator (csrc/lz_triplane_enc.hip).  Additive under ABI version 11.
  * Replaces NeRFNetwork.encode_x, nerf_triplane/network.py:208-223 (split_xyz, three GridEncoder calls, torch.cat), and per plane the
  * Python side of the operator, gridencoder/grid.py:18-84 (the [0, 1] mapping of grid.py:143 included), for three D = 2, C = 1, f32,

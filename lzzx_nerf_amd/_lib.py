@@ -98,6 +98,7 @@ SIGNATURES = {
     "lz_grid_encode_backward": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp],
     "lz_grid_encode_backward_ordered": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp, u32, u32, vp],
     "lz_grid_encode_backward_ordered_strided": [vp, u32, vp, vp, vp, u32, u32, u32, u32, f32, u32, u32, i32, vp, u32, u32, vp],
+    "lz_grid_encode_backward_fixed": [vp, vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, vp, u32, i32, i32, i32, vp, u32, u32, u32, vp],
     # the three-plane encoder (csrc/lz_triplane_enc.hip, lzzx_nerf_amd/gridencoder.py: TriplaneEncoder)
     "lz_triplane_encode_forward": [vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, u32, f32, vp],
     "lz_triplane_encode_backward": [vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, f32, u32, f32, vp],
@@ -212,7 +213,7 @@ PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_dev
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
          "lz_audio_train_workspace": ([], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
-         "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t)}
+         "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

@@ -1019,6 +1019,17 @@ extern "C" int lz_grid_encode_backward(const void* grad, const float* inputs, co
     return LZ_OK;
 }
 
+void lz_grid_input_backward_f32(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                bool sample_major, hipStream_t st) {
+    const dim3 g(lz_div_up((uint64_t)B * D, 256)), blk(256);
+#define LZ_GIN_F32(DD, CC) hipLaunchKernelGGL((lz_k_grid_input_backward<float, DD, CC>), g, blk, 0, st, grad, dy_dx, grad_inputs, B, L, sample_major)
+    if (D == 2u && C == 1u) LZ_GIN_F32(2, 1);
+    else if (D == 2u && C == 2u) LZ_GIN_F32(2, 2);
+    else if (D == 3u && C == 1u) LZ_GIN_F32(3, 1);
+    else if (D == 3u && C == 2u) LZ_GIN_F32(3, 2);
+#undef LZ_GIN_F32
+}
+
 // ---- ordered table gradient: no float atomics, the CPU checker's summation order (gridencoder.cu:226-313) ---------------------------
 // The checker adds the terms of a table entry one after another over (level, sample ascending, corner ascending) with a plain f32
 // `+= w * g`.  Here a level's terms -- one per (sample b, corner idx), rank t = b * 2^D + idx -- are sorted by entry with a STABLE least-

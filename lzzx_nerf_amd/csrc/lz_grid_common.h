@@ -167,4 +167,9 @@ __device__ __forceinline__ uint32_t lz_grid_corner_index(const LzGridLevel& lvl,
     }
     return lz_grid_corner<D>(term, idx, lvl.mode, lvl.hs) * C;
 }
+
+// lz_grid.hip: launches its lz_k_grid_input_backward<float, D, C> (kernel_input_backward, gridencoder.cu:316-342) for D 2 / 3 and C 1 / 2,
+// for the entry of lz_grid_fixed.hip; nothing is launched for other shapes
+void lz_grid_input_backward_f32(const float* grad, const float* dy_dx, float* grad_inputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                                bool sample_major, hipStream_t st);
 #endif

@@ -17,8 +17,10 @@ _gridtype_to_id = {"hash": 0, "tiled": 1}
 
 # How the table gradient is summed: "atomic" = float atomics (the reference's way: repeatable only up to summation order), "ordered" =
 # lz_grid_encode_backward_ordered: no float atomics, every entry summed in the CPU checker's (sample, corner) order, the same bits on
-# every call (f32 tables, D 2 / 3).
-_TABLE_GRADS = ("atomic", "ordered")
+# every call (f32 tables, D 2 / 3), "fixed" = lz_grid_encode_backward_fixed: every term quantised with one power-of-two scale per level and
+# summed as 64-bit integers, one rounding at the end -- the same bits on every call AND under any order of the rows (f32 tables, D 2 / 3,
+# C 1 / 2).
+_TABLE_GRADS = ("atomic", "ordered", "fixed")
 _TABLE_GRAD = "atomic"
 ORDERED_WORKSPACE_CAP = 256 << 20   # bytes; a batch whose level needs more is processed in sample ranges (same bits)
 
@@ -49,6 +51,32 @@ def grid_backward_ordered(grad, inputs, embeddings, offsets, grad_embeddings, B,
     call("lz_grid_encode_backward_ordered", ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_embeddings), B, D, C, L, S, H,
          ptr(dy_dx), ptr(grad_inputs), int(gridtype), int(bool(align_corners)), int(embeddings.dtype == torch.float16), grad_layout,
          ptr(ws), nbytes & 0xFFFFFFFF, nbytes >> 32, stream())
+
+
+def _check_fixed(D, C, dtype):
+    """what lz_grid_encode_backward_fixed does not serve, refused with the modes that do"""
+    if dtype != torch.float32:
+        raise RuntimeError("set_table_grad('fixed') sums f32 tables only; half tables (autocast with an even level_dim) take the atomic "
+                           "path: set_table_grad('atomic') or leave autocast")
+    if D not in (2, 3):
+        raise RuntimeError("set_table_grad('fixed') is built for input_dim 2 and 3 (got %d): set_table_grad('atomic') serves every input_dim" % D)
+    if C not in (1, 2):
+        raise RuntimeError("set_table_grad('fixed') is built for level_dim 1 and 2 (got %d): set_table_grad('atomic') or 'ordered' serve "
+                           "level_dim 4 and 8" % C)
+
+
+def grid_backward_fixed(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype, align_corners,
+                        grad_layout, grad_row_stride=0, workspace_bytes=None):
+    """lz_grid_encode_backward_fixed on a per-device cached workspace of lz_grid_fixed_workspace(entries of the table, C) bytes (the cache
+    keeps the largest size asked for so far; the call clears what it uses); workspace_bytes overrides the size.  grad may be a tensor or,
+    for a block of columns of a wider matrix, a device address (with grad_row_stride)"""
+    _check_fixed(D, C, embeddings.dtype)
+    need = int(_lib.load().lz_grid_fixed_workspace(grad_embeddings.shape[0], C))
+    nbytes = need if workspace_bytes is None else int(workspace_bytes)
+    ws = workspace("grid_fixed", grad_embeddings.device, nbytes, grow=True)
+    call("lz_grid_encode_backward_fixed", grad if isinstance(grad, int) else ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets),
+         ptr(grad_embeddings), B, D, C, L, S, H, ptr(dy_dx), ptr(grad_inputs), int(gridtype), int(bool(align_corners)), 0, grad_layout, ptr(ws),
+         nbytes & 0xFFFFFFFF, nbytes >> 32, int(grad_row_stride), stream())
 
 
 def _check_dc(D, C):
@@ -134,6 +162,11 @@ class _grid_encode(Function):
                                    "atomic path: set_table_grad('atomic') or leave autocast")
             grid_backward_ordered(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
                                   ctx.align_corners, 1)
+            return grad_inputs, grad_embeddings, None, None, None, None, None, None
+        if _TABLE_GRAD == "fixed":
+            _check_fixed(D, C, embeddings.dtype)
+            grid_backward_fixed(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                                ctx.align_corners, 1)
             return grad_inputs, grad_embeddings, None, None, None, None, None, None
         call("lz_grid_encode_backward", ptr(grad), ptr(inputs), ptr(embeddings), ptr(offsets), ptr(grad_embeddings), B, D, C, L,
              S, H, ptr(dy_dx), ptr(grad_inputs), int(gridtype), int(bool(ctx.align_corners)),
@@ -231,20 +264,26 @@ class _triplane_encode(Function):
         want_tables = any(ctx.needs_input_grad[1:4])
         g_tables = [torch.zeros_like(t) for t in tables] if want_tables else [None] * 3
         g_xyz = torch.empty_like(xyz) if dy_dx is not None else None
-        ordered = _TABLE_GRAD == "ordered" and want_tables and B > 0
-        if ordered:
-            # the checker's summation order per plane (lz_grid_encode_backward_ordered_strided); the plane's [0, 1] coordinates as the
-            # three-encoder path forms them
+        per_plane = _TABLE_GRAD if (_TABLE_GRAD != "atomic" and want_tables and B > 0) else None
+        if per_plane is not None:
+            # the checker's summation order ("ordered", lz_grid_encode_backward_ordered_strided) or the order-free integer sum ("fixed",
+            # lz_grid_encode_backward_fixed with a row stride) per plane, on the plane's [0, 1] coordinates as the three-encoder path
+            # forms them and on the plane's columns of the [B, 3 L] gradient where they lie
             unit = map01(xyz, bound)
-            need = int(_lib.load().lz_grid_ordered_workspace(B, 2))
-            nbytes = min(need, ORDERED_WORKSPACE_CAP)
-            ws = workspace("grid_ordered", xyz.device, nbytes, grow=True)
+            if per_plane == "ordered":
+                need = int(_lib.load().lz_grid_ordered_workspace(B, 2))
+                nbytes = min(need, ORDERED_WORKSPACE_CAP)
+                ws = workspace("grid_ordered", xyz.device, nbytes, grow=True)
             for plane, cols in enumerate(((0, 1), (1, 2), (0, 2))):
                 uv = unit[:, cols].contiguous()
-                call("lz_grid_encode_backward_ordered_strided", grad.data_ptr() + 4 * plane * L, 3 * L, ptr(uv), ptr(offsets), ptr(g_tables[plane]),
-                     B, 2, 1, L, S, H, 0, 0, ptr(ws), nbytes & 0xFFFFFFFF, nbytes >> 32, stream())
-        if (want_tables and not ordered) or g_xyz is not None:
-            gt = [None] * 3 if ordered else g_tables
+                if per_plane == "ordered":
+                    call("lz_grid_encode_backward_ordered_strided", grad.data_ptr() + 4 * plane * L, 3 * L, ptr(uv), ptr(offsets),
+                         ptr(g_tables[plane]), B, 2, 1, L, S, H, 0, 0, ptr(ws), nbytes & 0xFFFFFFFF, nbytes >> 32, stream())
+                else:
+                    grid_backward_fixed(grad.data_ptr() + 4 * plane * L, uv, tables[plane], offsets, g_tables[plane], B, 2, 1, L, S, H, None,
+                                        None, 0, False, 1, grad_row_stride=3 * L)
+        if (want_tables and per_plane is None) or g_xyz is not None:
+            gt = [None] * 3 if per_plane is not None else g_tables
             call("lz_triplane_encode_backward", ptr(grad), ptr(xyz), ptr(offsets), ptr(gt[0]), ptr(gt[1]), ptr(gt[2]), ptr(dy_dx), ptr(g_xyz), B, L,
                  S, H, bound, stream())
         return (g_xyz, g_tables[0], g_tables[1], g_tables[2], None, None, None, None, None)

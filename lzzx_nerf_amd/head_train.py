@@ -226,6 +226,8 @@ class _FusedHeadTrain(Function):
                 dx01.append(gin)
             if gridencoder.table_grad() == "ordered":   # no float atomics, the checker's order (gridencoder.set_table_grad)
                 gridencoder.grid_backward_ordered(g, c, e, mod.offsets, ge, M, 2, 1, 12, mod.S, mod.H, jac, gin, 0, False, 0)
+            elif gridencoder.table_grad() == "fixed":   # 64-bit integer sums with one scale per level: free of the rows' order as well
+                gridencoder.grid_backward_fixed(g, c, e, mod.offsets, ge, M, 2, 1, 12, mod.S, mod.H, jac, gin, 0, False, 0)
             else:
                 call("lz_grid_encode_backward", ptr(g), ptr(c), ptr(e), ptr(mod.offsets), ptr(ge), M, 2, 1, 12, mod.S, mod.H, ptr(jac), ptr(gin),
                      0, 0, 0, 3 if M >= 16384 else 0, stream())

@@ -6,6 +6,7 @@ rgb = sigmoid) as an autograd Function over fused kernels instead of ~25 operato
     backward  lz_ngp_head_backward (csrc/lz_ngp_train.hip: recomputes the head, every MLP gradient on the matrix cores, a fixed-order
               combine of the weight gradients) -> lz_grid_encode_backward (grad_layout 0: the table scatter, float atomics), or with
               table_grad "ordered" lz_grid_encode_backward_ordered (no float atomics, the CPU checker's summation order)
+              table_grad "fixed"   lz_grid_encode_backward_fixed (64-bit integer sums, one scale per level: free of the samples' order)
 
 Scope: f32 arithmetic and f32 tables at the fixed cfg2 shape; no position / direction gradient.  What is not built is refused with an
 error, never answered with a silently wrong gradient."""
@@ -83,9 +84,13 @@ class _NgpTrain(Function):
                  ptr(g_rgb), ptr(d_feats), *[ptr(g) for g in gws], ptr(_workspace(dev)), stream())
             # the gather's own mapping (lz_grid_unit -> lz_map01): torch's division by a host scalar, measured to be a reciprocal multiply
             unit = map01(xyzs, meta["bound"])
-            if (meta["table_grad"] or gridencoder.table_grad()) == "ordered":
+            mode = meta["table_grad"] or gridencoder.table_grad()
+            if mode == "ordered":
                 gridencoder.grid_backward_ordered(d_feats, unit, emb, meta["offsets"], g_emb, M, 3, 2, 16, meta["S"], meta["H"], None, None, 0,
                                                   False, 0)
+            elif mode == "fixed":
+                gridencoder.grid_backward_fixed(d_feats, unit, emb, meta["offsets"], g_emb, M, 3, 2, 16, meta["S"], meta["H"], None, None, 0,
+                                                False, 0)
             else:
                 call("lz_grid_encode_backward", ptr(d_feats), ptr(unit), ptr(emb), ptr(meta["offsets"]), ptr(g_emb), M, 3, 2, 16, meta["S"],
                      meta["H"], None, None, 0, 0, 0, 0, stream())
@@ -111,7 +116,9 @@ class FusedHashgridTrainNeRF(nn.Module):
     table_grad: how the table gradient is summed.  "atomic" = float atomics, repeatable only up to summation order; "ordered" = every
     table entry summed without atomics in the CPU checker's (sample, corner) order.  With "ordered" the whole backward repeats bit for
     bit -- `encoder.embeddings.grad` and the four weight gradients are the same bits on every call from the same inputs, and the table
-    gradient equals oracle.grid_encode_backward on the d_feats of the backward -- at the price of a sort per level.  None (the default)
+    gradient equals oracle.grid_encode_backward on the d_feats of the backward -- at the price of a sort per level.  "fixed" = every
+    term quantised with one power-of-two scale per level and summed as 64-bit integers (lz_grid_encode_backward_fixed): the backward
+    repeats bit for bit as well, and the table gradient does not depend on the order of the samples either.  None (the default)
     follows gridencoder.set_table_grad, read at every backward.
 
     Refused: inputs that require grad (no position / direction gradient), autocast, half tables, other encoder or MLP shapes."""

@@ -1,5 +1,6 @@
-"""The ordered table gradient (lz_grid_encode_backward_ordered: sort + segmented sequential sum, no float atomics) against the atomic
-scatter (lz_grid_encode_backward) it is an alternative to, on two shapes:
+"""The ordered table gradient (lz_grid_encode_backward_ordered: sort + segmented sequential sum, no float atomics) and the order-free one
+(lz_grid_encode_backward_fixed: 64-bit integer sums with one scale per level) against the atomic scatter (lz_grid_encode_backward) they
+are alternatives to, on two shapes:
 
     cfg2    the BASELINE cfg2 training batch: 256 x 256 rays, march_rays_train with max_steps 128, D 3, C 2, L 16, T 19, gradient [L, B, C]
     plane   one plane of the triplane head on the same samples' (x, y): D 2, C 1, L 12, T 14, gradient [L, B, C] (the LDS scatter)
@@ -7,7 +8,7 @@ scatter (lz_grid_encode_backward) it is an alternative to, on two shapes:
 The variants alternate; each round times `--iters` calls per variant, every timed step under its own time limit (`--limit` seconds: the
 process exits with status 3 when a step has not finished by then); the median over `--rounds` rounds is printed as one JSON line (and
 written to `--out`).  Per-kernel time: run under `rocprofv3 --kernel-trace --stats -- python tools/grid_ordered_bench.py --iters 1
---rounds 1`."""
+--rounds 1` (`--only fixed` leaves the other two variants out of the trace)."""
 import argparse
 import json
 import os
@@ -49,6 +50,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--limit", type=float, default=60.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default=None, help="comma-separated variants to run (atomic, ordered, fixed); default all, with the ratios")
     a = ap.parse_args()
     H = W = a.size
     pose, intr = synthetic_camera(H, W)
@@ -80,23 +82,32 @@ def main():
             ge.zero_()
             gridencoder.grid_backward_ordered(g, x, enc.embeddings, enc.offsets, ge, M, D, C, L, S, Hres, None, None, 0, False, 0)
 
+        def fixed(enc=enc, x=x, g=g, ge=ge, D=D, C=C, L=L, S=S, Hres=Hres):
+            ge.zero_()
+            gridencoder.grid_backward_fixed(g, x, enc.embeddings, enc.offsets, ge, M, D, C, L, S, Hres, None, None, 0, False, 0)
+
         need = int(_lib.load().lz_grid_ordered_workspace(M, D))
-        shapes[name] = dict(D=D, C=C, L=L, atomic=atomic, ordered=ordered, need=need)
-    for s in shapes.values():                 # warm-up: allocations, the workspace
-        s["atomic"]()
-        s["ordered"]()
+        shapes[name] = dict(D=D, C=C, L=L, atomic=atomic, ordered=ordered, fixed=fixed, need=need,
+                            need_fixed=int(_lib.load().lz_grid_fixed_workspace(enc.embeddings.shape[0], C)))
+    variants = [v for v in ("atomic", "ordered", "fixed") if a.only is None or v in a.only.split(",")]
+    for s in shapes.values():                 # warm-up: allocations, the workspaces
+        for v in variants:
+            s[v]()
     torch.cuda.synchronize()
     res = {"rays": H * W, "samples": M, "rounds": a.rounds, "iters": a.iters}
     for name, s in shapes.items():
-        times = {"atomic": [], "ordered": []}
+        times = {v: [] for v in variants}
         for _ in range(a.rounds):
             for k in times:
                 times[k].append(timed(s[k], a.iters, a.limit))
         for k, v in times.items():
             res["%s_%s_ms" % (name, k)] = round(float(np.median(v)), 4)
-        res["%s_ordered_over_atomic" % name] = round(res["%s_ordered_ms" % name] / res["%s_atomic_ms" % name], 2)
+        for num, den in (("ordered", "atomic"), ("fixed", "atomic"), ("fixed", "ordered")):
+            if num in times and den in times:
+                res["%s_%s_over_%s" % (name, num, den)] = round(res["%s_%s_ms" % (name, num)] / res["%s_%s_ms" % (name, den)], 3 if den == "ordered" else 2)
         res["%s_workspace_unchunked_bytes" % name] = s["need"]
         res["%s_workspace_used_bytes" % name] = min(s["need"], gridencoder.ORDERED_WORKSPACE_CAP)
+        res["%s_fixed_workspace_bytes" % name] = s["need_fixed"]
     line = json.dumps(res)
     print(line)
     if a.out:
