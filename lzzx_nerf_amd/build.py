@@ -28,7 +28,23 @@ RESOURCES = os.path.join(LIBDIR, "kernel_resources.json")
 # backward chains into v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 (47-71 of them per backward kernel), and packed f32 vector ops cost more
 # issue time than the scalar pair they replace next to MFMA work (MI355X_MICROARCH.md; lz_head_gather.h).  Same-box A/B of the cfg3 step,
 # three alternations: f32-exact 12.21 -> 12.08 ms, -O 5.88 -> 5.82; same bits (the lanes of a packed op are independent IEEE operations).
-FILE_FLAGS = {"lz_head_rec.hip": ["-fno-slp-vectorize"]}
+# On the inference heads (lz_frame.hip, lz_head.hip) it removes the 40 v_pk_fma_f32 per slice that the vectoriser makes of the eye and
+# ind_code k-steps on the VALU: the f32 frame 8.556 -> 8.414 ms in the same kind of A/B (profiles/r7_lean_stream_ab.json), and
+# it is what lets the folded kernels run the ind_code k-step on the VALU without a spill (lz_head_slice.h).
+FILE_FLAGS = {"lz_head_rec.hip": ["-fno-slp-vectorize"], "lz_frame.hip": ["-fno-slp-vectorize"], "lz_head.hip": ["-fno-slp-vectorize"]}
+# Further compilations of one source into objects of their own, {source: {part: flags behind FLAGS + FILE_FLAGS}}; their kernels are
+# reported under the source's name in lib/kernel_resources.json.  lz_frame.hip's f16 kernels are built WITH the vectoriser: that kernel
+# is bound by vector issue, and splitting its 14 packed operations costs the f16 frame 0.2 - 0.7 %.
+FILE_PARTS = {"lz_frame.hip": {"f16": ["-DLZF_F16_TU", "-fslp-vectorize"]}}
+
+
+def _jobs(sources=None):
+    """(source, object name, flags behind FLAGS + FILE_FLAGS) of every compilation"""
+    out = []
+    for src in SOURCES if sources is None else sources:
+        out.append((src, src.replace(".hip", ".o"), []))
+        out += [(src, src.replace(".hip", "_%s.o" % part), list(fl)) for part, fl in FILE_PARTS.get(src, {}).items()]
+    return out
 
 
 def _hipcc():
@@ -78,19 +94,20 @@ def build(force=False, verbose=False):
 
     resources = {}
 
-    def compile_one(src):
-        obj = os.path.join(OBJDIR, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
+    def compile_one(job):
+        src, oname, part_flags = job
+        obj = os.path.join(OBJDIR, oname)
+        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(src, []) + part_flags + ["-c", os.path.join(CSRC, src), "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed for %s:\n%s" % (src, r.stderr))
-        resources[src] = parse_resources(r.stderr)
+        resources.setdefault(src, {}).update(parse_resources(r.stderr))
         if verbose and r.stderr:
             print("\n".join(l for l in r.stderr.splitlines() if "kernel-resource-usage" not in l), file=sys.stderr)
         return obj
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(compile_one, SOURCES))
+        objs = list(ex.map(compile_one, _jobs()))
     import json
     with open(RESOURCES, "w") as f:   # a register spill in a kernel tuned to a register limit is a 1.5x slowdown that no parity test sees:
         json.dump(resources, f, indent=1, sort_keys=True)   # tests/test_cabi.py checks this report
@@ -111,11 +128,12 @@ def build_variant(name, extra_flags, only=None):
     hipcc = _hipcc()
     objs = []
 
-    def one(src):
+    def one(job):
+        src, oname, part_flags = job
         if only is not None and src not in only:
-            return os.path.join(OBJDIR, src.replace(".hip", ".o"))
-        obj = os.path.join(odir, src.replace(".hip", ".o"))
-        r = subprocess.run([hipcc] + FLAGS + FILE_FLAGS.get(src, []) + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", obj], capture_output=True, text=True)
+            return os.path.join(OBJDIR, oname)
+        obj = os.path.join(odir, oname)
+        r = subprocess.run([hipcc] + FLAGS + FILE_FLAGS.get(src, []) + part_flags + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", obj], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed for %s:\n%s" % (src, r.stderr))
         res = parse_resources(r.stderr)
@@ -125,7 +143,7 @@ def build_variant(name, extra_flags, only=None):
         return obj
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        objs = list(ex.map(one, SOURCES))
+        objs = list(ex.map(one, _jobs()))
     so = os.path.join(vdir, name + ".so")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so] + objs, capture_output=True, text=True)
     if r.returncode != 0:

@@ -53,6 +53,10 @@
 #define LZF_WAVES (LZF_WG / 64)
 #define LZF_MARCH_PROBES 2   // empty cells a slot may cross per march attempt (S = 1); measured on cfg5 (f16 / f32 ms): 1 -> 1.80 / 4.30, 2 -> 1.82 / 4.29, 3 -> 1.83 / 4.34, 6 -> 1.84 / 4.38, 12 -> 1.96 / 4.49, unbounded -> 2.39 / 4.81
 
+// This file is compiled twice (build.py: FILE_PARTS).  Without LZF_F16_TU: everything but the f16 frame kernels, without the SLP vectoriser
+// (the f32 slices' VALU k-steps must stay scalar).  With it: only lz_k_frame<1, S, 2> and their launcher, WITH the vectoriser -- that
+// kernel is bound by vector issue and its 14 packed operations pay (f16 frame 0.2 - 0.7 % slower without them).
+#ifndef LZF_F16_TU
 // ---- pass 1: near / far, first occupied cell, sort key, histogram -------------------------------------------------------------
 // (1 024 rays per workgroup in both small passes: each workgroup ends with one global atomic per non-empty key, and same-address atomics
 // serialise in the L2 at ~80 ns each -- with 256-ray workgroups a 512^2 frame queued ~1 000 of them on every popular key)
@@ -179,6 +183,8 @@ __global__ void __launch_bounds__(LZF_C1SH_WG) lz_k_frame_c1sh(const float* __re
         for (int ft = 0; ft < 4; ft++) *reinterpret_cast<lz_f4*>(row + 4 * ft) = acc[ft][0];
     }
 }
+
+#endif  // !LZF_F16_TU
 
 // ---- pass 3: the persistent kernel --------------------------------------------------------------------------------------------
 // slot state in LDS, per wave [field][16]
@@ -711,6 +717,19 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
 #undef cnt_base
 #undef LZF_RF
 
+// the f16 kernels' launcher: S = 1, 2, 4, 8 or 16, checked by the caller
+void lzf_launch_f16(uint32_t S, uint32_t grid, hipStream_t st, const LzHead16Args& a, const LzFrameK& K);
+#ifdef LZF_F16_TU
+void lzf_launch_f16(uint32_t S, uint32_t grid, hipStream_t st, const LzHead16Args& a, const LzFrameK& K) {
+    switch (S) {
+        case 1: hipLaunchKernelGGL((lz_k_frame<1, 1, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
+        case 2: hipLaunchKernelGGL((lz_k_frame<1, 2, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
+        case 4: hipLaunchKernelGGL((lz_k_frame<1, 4, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
+        case 8: hipLaunchKernelGGL((lz_k_frame<1, 8, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
+        default: hipLaunchKernelGGL((lz_k_frame<1, 16, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
+    }
+}
+#else
 // ---- the reference's cap (cap_mode 1): histogram of L, schedule replay, marched counts ------------------------------------------------
 // cap_ws: [0 .. max_steps] histogram of L (bin max_steps = rays alive at the cap); behind it the schedule tables, see lzf_ws_*
 __host__ __device__ __forceinline__ int lzf_ws_chunk_end(int max_steps) { return max_steps + 1; }     // [max_steps + 9]: index c = 1-based sample
@@ -1145,13 +1164,7 @@ static int lzf_launch_persistent(const lz_frame_fused* f, const LzFrameK& K, hip
         // f16: two slot rows (32 slots) per wave at every S -- the head works on 32-sample slices (lz_head16w_slice), and the march / refill /
         // compositing sections cost the same instructions for 16 or 32 active lanes.  (Rounds 2-4 also had one- and three-row layouts on
         // 16-sample slices; the 32x32x16 slice halves the MFMA issue slots instead: DESIGN 4.1b.)
-        switch (S) {
-            case 1: hipLaunchKernelGGL((lz_k_frame<1, 1, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
-            case 2: hipLaunchKernelGGL((lz_k_frame<1, 2, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
-            case 4: hipLaunchKernelGGL((lz_k_frame<1, 4, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
-            case 8: hipLaunchKernelGGL((lz_k_frame<1, 8, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
-            default: hipLaunchKernelGGL((lz_k_frame<1, 16, 2>), dim3(grid), dim3(LZF_WG), 0, st, a, K); break;
-        }
+        lzf_launch_f16(S, grid, st, a, K);     // (the f16 kernels live in this file's other compilation: LZF_F16_TU)
     } else {
         LzHeadArgs a;
         a.emb[0] = p->emb_xy; a.emb[1] = p->emb_yz; a.emb[2] = p->emb_xz;
@@ -1225,3 +1238,4 @@ extern "C" int lz_frame_render(const lz_frame_fused* f, lz_timing* timing, lz_st
     if (ref_cap && !f->defer_finish) return lzf_finish(f, st, c1sh.p);
     return LZ_OK;
 }
+#endif  // LZF_F16_TU

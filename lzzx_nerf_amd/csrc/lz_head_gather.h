@@ -20,12 +20,17 @@
 // PACK (the interpolation on v_pk_mul_f32 / v_pk_fma_f32, two features per instruction) is OFF in every head since round 4: fewer instructions
 // but slower ones -- packed f32 vector ops cost more issue time than the two scalar ones they replace next to MFMA work
 // (MI355X_MICROARCH.md, "packed f32 VALU ... an anti-lever beside MFMAs").  Same-box A/B on the fused frame: f16 1.916 -> 1.894 ms, f32
-// 8.92 -> 8.88.  (-fno-slp-vectorize, which removes the compiler's own two dozen packed ops as well: no further gain.)
+// 8.92 -> 8.88.  (-fno-slp-vectorize, which removes the compiler's own packed ops as well, gave no further gain then; since the eye and
+// ind_code k-steps run on the VALU it does, and lz_frame.hip / lz_head.hip are built with it: build.py, FILE_FLAGS.)
 #ifndef LZ_GATHER_PACK16
 #define LZ_GATHER_PACK16 false
 #endif
 #ifndef LZ_GATHER_PACK32
 #define LZ_GATHER_PACK32 false
+#endif
+// A/B switch of the dense pairs' load form (PAIR0 below): 1 = one 8-byte buffer load per row, 0 = the 8-byte memcpy it replaced
+#ifndef LZ_GATHER_PAIR_BUF
+#define LZ_GATHER_PAIR_BUF 1
 #endif
 #include "lz_common.h"
 #include "lzzx_detmath.h"
@@ -72,6 +77,7 @@ __device__ __forceinline__ void lz_level_table_fill(int* tab, const int* __restr
 }
 
 typedef float lz_gf2 __attribute__((ext_vector_type(2)));
+typedef uint32_t lz_gu2 __attribute__((ext_vector_type(2)));
 
 // tab: the table above; emb: the three planes' tables; (px, py, pz): the sample
 // IN_RANGE drops the range clamps / out-of-range selects for a caller that guarantees |x|, |y|, |z| <= bound -- the fused f16 frame kernel,
@@ -83,8 +89,11 @@ typedef float lz_gf2 __attribute__((ext_vector_type(2)));
 // priority drops once they are issued and the matrix phase behind them yields to the other waves' address work (fused f32 frame kernel:
 // 9.17 -> 8.99 ms; dropping it before the address arithmetic instead: 9.06; no effect on the issue-bound f16 kernel)
 // PAIR0: when levels 0..3 are dense (LZ_LVTAB_DENSE0; every lane's first level record), their x / x + 1 corners are adjacent table entries
-// and come with one 8-byte load per row: 30 load instructions per lane instead of 36 and 18 index instructions less.  Same-box A/B on
-// the fused frame: f32 9.05 -> 8.97 ms, f16 2.025 -> 2.04 ms (no gain: the f16 slices keep the one-load-per-corner form)
+// and come with one 8-byte load per row: per plane 2 buffer_load_dwordx2 off a descriptor of the plane with 2 v_add_lshl_u32 in front,
+// inside the dense branch -- 30 load instructions per lane instead of 36.  (First written as an 8-byte memcpy through a pointer, recorded
+// at f32 9.05 -> 8.97 ms; later compilers split that memcpy into two dword loads and sank all four loads of a plane into the block where
+// the two branches meet, with 64-bit phi addresses: 4 loads, 4 v_lshl_add_u64 and 4 more index instructions per plane, no pair in the
+// binary.  tests/test_frame_isa_host.py counts the pairs now.)  The f16 slices keep the one-load-per-corner form (f16 2.025 -> 2.04 ms)
 // LSTRIDE: the lane's three level records are levels q + LSTRIDE mrec (mrec < 3).  4: the 16-sample heads (lane group q of four owns features
 // 4 i + q).  2: the 32-sample f16 head (lz_head_f16w_slice.h), whose lane half h owns 18 features in two calls, q = h and q = 6 + h.
 // (x + bound) / (2 bound) of a sample, grid.py:143 -- what lz_head_gather starts with; a caller that gathers one sample in several calls
@@ -167,6 +176,7 @@ __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], con
     float gv[9][4];
     static_assert(!PAIR0 || LSTRIDE == 4, "PAIR0 pairs the corners of levels 0..3");
     const bool dense0 = PAIR0 && __builtin_amdgcn_readfirstlane(tab[LZ_LVTAB_DENSE0]) != 0;     // workgroup-uniform, a scalar branch
+    const uint32_t plane_bytes = PAIR0 ? (uint32_t)__builtin_amdgcn_readfirstlane(tab[12]) << 2 : 0u;   // read with dense0: one LDS wait for both
 #pragma unroll
     for (int i = 0; i < 9; i++) {
         constexpr int kPlaneOf[9] = {0, 0, 0, 1, 1, 1, 2, 2, 2};
@@ -176,8 +186,19 @@ __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], con
         const char* gb = reinterpret_cast<const char*>(emb[plane]);
         const uint32_t g0 = cell[mrec][cd];
         if (mrec == 0 && dense0) {
-            // dense level: entry = column + row term, and the x + 1 corner is the NEXT entry -- one 8-byte load per row (4-byte aligned:
-            // global_load_dwordx2 takes it) instead of two loads and two index computations: 30 load instructions per lane instead of 36
+            // dense level: entry = column + row term, and the x + 1 corner is the NEXT entry -- one 8-byte load per row instead of two loads
+            // and two index computations.  A buffer load (32-bit byte offset off a wave-uniform descriptor of the plane) and not a
+            // memcpy through a pointer: the compiler splits that into two dword loads and sinks them out of this branch (see PAIR0 above).
+            // The descriptor spans the whole plane (its last level offset, tab[12], entries), so a stray index reads 0 instead of leaving it.
+#if LZ_GATHER_PAIR_BUF
+            const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(gb), 0, plane_bytes, 0x00020000);
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const lz_gu2 pr = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (g0 + rowD[rc][0][r]) << 2, 0, 0);
+                gv[i][2 * r] = __uint_as_float(pr[0]);
+                gv[i][2 * r + 1] = __uint_as_float(pr[1]);
+            }
+#else
 #pragma unroll
             for (int r = 0; r < 2; r++) {
                 struct __attribute__((packed, aligned(4))) Pair { float a, b; } pr;
@@ -185,6 +206,7 @@ __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], con
                 gv[i][2 * r] = pr.a;
                 gv[i][2 * r + 1] = pr.b;
             }
+#endif
             continue;
         }
 #pragma unroll

@@ -114,6 +114,39 @@ struct LzShPartial {
     __device__ __forceinline__ lz_f4 part(int ft) const { return p[ft]; }
 };
 
+// The slice's ReLU as ONE integer instruction (v_max_i32): max((int)bits(v), 0).  lz_relu (`v > 0 ? v : 0`) on an MFMA result compiles to
+// two v_max_f32 -- a canonicalising v_max_f32 v, v, v, which the compiler cannot prove away for MFMA outputs, and the maximum itself -- 68
+// times per slice between the MFMAs.  Same bits for every f32 that is no NaN: -0 and every negative value have the sign bit set, a negative
+// integer, and become +0; +0, positive denormals, normals and +inf are positive integers and pass.  A NaN of positive sign PASSES (lz_relu
+// turns every NaN into 0; np.maximum in oracle/head.py passes it too); a NaN of negative sign becomes +0.  For lz_head_slice only: the
+// training chains keep lz_relu (the shared helper changed this way costs lz_k_triplane_head_forward_rec 32 registers and a spill).
+// LZ_SLICE_RELU_I32 = 0 restores lz_relu (A/B switch).
+#ifndef LZ_SLICE_RELU_I32
+#define LZ_SLICE_RELU_I32 1
+#endif
+__device__ __forceinline__ float lz_slice_relu(float v) {
+#if LZ_SLICE_RELU_I32
+    const int b = (int)__float_as_uint(v);
+    return __uint_as_float((uint32_t)(b > 0 ? b : 0));
+#else
+    return lz_relu(v);
+#endif
+}
+
+// Behind each ReLU block of the slice: no vector instruction and no MFMA crosses (scalar, LDS and memory instructions do).  Left alone the
+// scheduler deals the ReLUs out one by one among the next layer's MFMAs, and beside f32 MFMAs it is OPENING a gap that is dear -- 7 cycles
+// per MFMA and SIMD for the first vector instruction of a gap, 2 to 2.5 for each further one (tools/probes/mfma_f32_fill_probe.hip).  With
+// the fence a layer's ReLUs stand together: gaps holding one vector instruction 39 -> 17 in lz_k_frame<0, 1, 1>, 120 -> 117 VGPRs, the
+// frame 0.3 % faster in every run of an A/B.  LZ_SLICE_RELU_FENCE = 0 takes it out (A/B switch).
+#ifndef LZ_SLICE_RELU_FENCE
+#define LZ_SLICE_RELU_FENCE 1
+#endif
+__device__ __forceinline__ void lz_slice_relu_fence() {
+#if LZ_SLICE_RELU_FENCE
+    __builtin_amdgcn_sched_barrier(0x94);
+#endif
+}
+
 // one slice: (px, py, pz) = this lane's sample position; shfn supplies SH(4) of its view direction when the colour net needs it
 // (LzShFromDir: evaluated here from the direction, like the reference per sample), or the colour net's SH partial of the sample's ray
 // (LzShPartial: the fused frame kernel, which evaluates k-steps 0 .. 3 of colour_net.0 once per ray)
@@ -146,7 +179,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
             for (int ft = 0; ft < 4; ft++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_relu(acc1[ft][j][r]);
+                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_slice_relu(acc1[ft][j][r]);
+        lz_slice_relu_fence();
         lz_f4 acc2[2][LZ_T];
 #pragma unroll
         for (int ft = 0; ft < 2; ft++)
@@ -184,7 +218,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
         for (int j = 0; j < LZ_T; j++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) be[j][r] = lz_relu(acce[0][j][r]);
+            for (int r = 0; r < 4; r++) be[j][r] = lz_slice_relu(acce[0][j][r]);
+        lz_slice_relu_fence();
 #pragma unroll
         for (int j = 0; j < LZ_T; j++) eyeatt[j] = lz_sigmoidf(lz_lane_dot<1>(hc.wl + WV + LZ_WV_E2, q, be[j]));
     }
@@ -203,7 +238,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
             for (int ft = 0; ft < 2; ft++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) bu[j][4 * ft + r] = lz_relu(accu[ft][j][r]);
+                for (int r = 0; r < 4; r++) bu[j][4 * ft + r] = lz_slice_relu(accu[ft][j][r]);
+        lz_slice_relu_fence();
 #pragma unroll
         for (int j = 0; j < LZ_T; j++) uncv[j] = lz_softplusf(lz_lane_dot<2>(hc.wl + WV + LZ_WV_U2, q, bu[j]));
     } else {
@@ -255,7 +291,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
             for (int ft = 0; ft < 4; ft++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_relu(acc1[ft][j][r]);
+                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_slice_relu(acc1[ft][j][r]);
+        lz_slice_relu_fence();
         shfn.issue(q);            // the per-ray SH partial of colour_net.0 (LzShPartial): its loads fly under sigma_net.1 / .2
         lz_f4 acc2[4][LZ_T];
 #pragma unroll
@@ -269,7 +306,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
             for (int ft = 0; ft < 4; ft++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) b3[j][4 * ft + r] = lz_relu(acc2[ft][j][r]);
+                for (int r = 0; r < 4; r++) b3[j][4 * ft + r] = lz_slice_relu(acc2[ft][j][r]);
+        lz_slice_relu_fence();
         if constexpr (FOLD) {
 #pragma unroll
             for (int j = 0; j < LZ_T; j++)
@@ -295,8 +333,6 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
     // ---------------- colour net: [SH 16 | geo 64 | ind 4] -> 64 -> 3 ----------------
     float rgb[LZ_T][3];
     {
-        // k-step 20 (ind_code) runs on the VALU (below), except with FOLD: there it spills the folded frame kernels, and stays an MFMA
-        constexpr bool IND_VALU = !FOLD;
         float b1[LZ_T][21];
         lz_f4 acc1[4][LZ_T];
 #pragma unroll
@@ -318,15 +354,16 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
             }
 #pragma unroll
             for (int k = 0; k < 16; k++) b1[j][4 + k] = geo[j][k];
-            b1[j][20] = IND_VALU ? 0.0f : hc.indq;     // (k-step 20, ind_code, runs on the VALU below unless FOLD)
+            b1[j][20] = 0.0f;           // (k-step 20, ind_code, runs on the VALU below)
         }
-        lz_layer_ks<LZ_L_C1, LZ_T, ShFn::C1_PARTIAL ? LZ_C1_SH_KS : 0, LZ_KS[LZ_L_C1] - (IND_VALU ? 1 : 0)>(hc.wl, lane, b1, acc1);
+        lz_layer_ks<LZ_L_C1, LZ_T, ShFn::C1_PARTIAL ? LZ_C1_SH_KS : 0, LZ_KS[LZ_L_C1] - 1>(hc.wl, lane, b1, acc1);
         // k-step 20 = the 4 ind_code inputs, the same for every sample and the last link of the chain: on the VALU, acc = fma(W[n, 80 + k],
         // ind[k], acc) for k = 0 .. 3 in the MFMA's order (an f32 MFMA is a k-ordered fma chain).  Lane (s, q) needs W[16 ft + 4 q + r, 80 + k]
         // = entries 16 k + 4 q .. 16 k + 4 q + 3 of the A fragment (20, ft): 16 ds_read_b128 and 64 fmas instead of 4 MFMAs (measured: the
         // f32 frame 1.1 % faster; the same move for a per-sample k-step, whose B values first cross lanes, was 3-6 % SLOWER).  Without
-        // ind_code the k-step adds zeros only: skipped.
-        if (IND_VALU && hc.has_ind) {
+        // ind_code the k-step adds zeros only: skipped.  (The folded kernels kept this k-step on the matrix pipe while the VALU form spilled
+        // them; built without the SLP vectoriser -- build.py: FILE_FLAGS -- it does not, and they issue 273 MFMAs per slice instead of 277.)
+        if (hc.has_ind) {
             const float* w80 = hc.wl + (lz_frag_base(LZ_L_C1) + 20 * LZ_NT[LZ_L_C1]) * 64 + 4 * q;
             const lz_f4 ind = *reinterpret_cast<const lz_f4*>(hc.lind);      // (one broadcast read)
 #pragma unroll
@@ -346,7 +383,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
             for (int ft = 0; ft < 4; ft++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_relu(acc1[ft][j][r]);
+                for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_slice_relu(acc1[ft][j][r]);
+        lz_slice_relu_fence();
         // colour_net.1 (64 -> 3) on the VALU (network.py:275), then the four transcendentals of a sample -- sigma = exp(h0) (network.py:302)
         // and three sigmoids (:310) -- ONE per lane instead of four per lane: after the lane-partial sums every lane of a sample holds all
         // four pre-activations, so lane q evaluates the q-th (q < 3: sigmoid = 1 / (1 + exp(-x)), q == 3: exp) with the same lz_expf on
