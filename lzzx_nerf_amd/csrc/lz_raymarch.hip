@@ -15,7 +15,7 @@
 //     frame needs no host synchronisation (the reference's `rays_alive[rays_alive >= 0]`, renderer.py:542,
 //     costs one device->host sync per iteration: 38 % of its loop time).
 //   * all kernels launch on the caller's stream.
-#include "lz_march.h"
+#include "lz_composite_train.h"
 
 // ------------------------------------------------------------------------------------------------
 // ray generation (nerf_triplane/utils.py:226-312): B poses x N pixels.  `inds` (pixel = row * W + col, shared by the batch like the
@@ -441,11 +441,7 @@ lz_k_march_train_count(const float* __restrict__ rays_o, const float* __restrict
     if (i >= N) return;
     const uint32_t n = order ? (uint32_t)order[i] : i;      // step-major layout: counts in PROCESSING order (counts[i] of ray order[i])
     LzMarch m;
-    m.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, grid);
-    if (H <= LZ_MORTON_LUT) m.morton_lut = mlut;
-    const float far = fars[n];
-    float t = nears[n];
-    t = lz_fmaf(lz_clampf(t * dt_gamma, m.dt_min, m.dt_max), noises[n], t);
+    float far, t = lz_march_train_start(m, rays_o, rays_d, n, bound, dt_gamma, max_steps, C, H, grid, mlut, nears, fars, noises, far);
     uint32_t num_steps = 0;
     float x, y, z, dt;
     while (t < far && num_steps < max_steps) {
@@ -534,9 +530,8 @@ __global__ void __launch_bounds__(LZ_MT_WG)
 lz_k_march_train_write(const float* __restrict__ rays_o, const float* __restrict__ rays_d, const uint8_t* __restrict__ grid,
                        float bound, float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M,
                        const float* __restrict__ nears, const float* __restrict__ fars, const float* __restrict__ noises,
-                       const int* __restrict__ offsets, const int* __restrict__ counts_next, const int* __restrict__ base,
-                       const int* __restrict__ total, float* __restrict__ xyzs, float* __restrict__ dirs,
-                       float* __restrict__ deltas, int* __restrict__ rays) {
+                       const int* __restrict__ offsets, const int* __restrict__ base, const int* __restrict__ total,
+                       float* __restrict__ xyzs, float* __restrict__ dirs, float* __restrict__ deltas, int* __restrict__ rays) {
     __shared__ uint32_t mlut[LZ_MORTON_LUT];
     lz_morton_lut_stage(mlut);
     __syncthreads();
@@ -550,42 +545,12 @@ lz_k_march_train_write(const float* __restrict__ rays_o, const float* __restrict
     __shared__ uint32_t srow[LZ_MT_WG / 64][64], scnt[LZ_MT_WG / 64][64];
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    bool active = n < N;
-    uint32_t num_steps = 0, point_index = 0;
-    if (active) {
-        // offsets[] holds the exclusive scan; the ray's own count is the difference to its successor
-        const uint32_t off = (uint32_t)offsets[n];
-        const uint32_t nxt = (n + 1 < N) ? (uint32_t)counts_next[n + 1] : (uint32_t)(total[0] - base[0]);
-        num_steps = nxt - off;
-        point_index = (uint32_t)base[0] + off;
-        const uint32_t ray_index = (uint32_t)base[1] + n;
-        rays[(size_t)ray_index * 3] = (int)n;
-        rays[(size_t)ray_index * 3 + 1] = (int)point_index;
-        rays[(size_t)ray_index * 3 + 2] = (int)num_steps;
-        if (num_steps == 0 || point_index + num_steps > M) active = false;     // nothing marched / dropped for lack of room (raymarching.cu:457)
-    }
-    // Rows nobody writes read ZERO, as the reference's wrapper left them (torch.zeros, raymarching.py:246-248) -- written here, so that the
-    // caller need not fill three sample buffers first (round 5: 3 of the 19 fill launches of a training step, ~190 MB): the rows of a ray that
-    // was dropped for lack of room, and (below) the tail behind the step's last row and anything in front of its first
-    auto zero_row = [&](uint32_t r) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) { xyzs[(size_t)r * 3 + k] = 0.0f; dirs[(size_t)r * 3 + k] = 0.0f; }
-        deltas[(size_t)r * 2] = 0.0f; deltas[(size_t)r * 2 + 1] = 0.0f;
-    };
-    if (n < N && num_steps != 0 && point_index + num_steps > M)
-        for (uint32_t r = point_index; r < M; r++) zero_row(r);
-    {
-        const uint32_t first = (uint32_t)base[0] < M ? (uint32_t)base[0] : M, last = (uint32_t)total[0] < M ? (uint32_t)total[0] : M;
-        const uint32_t nthreads = gridDim.x * blockDim.x, span = first + (M - last);
-        for (uint32_t i = n; i < span; i += nthreads) zero_row(i < first ? i : last + (i - first));
-    }
+    uint32_t num_steps = 0, point_index = 0;     // num_steps: the rows to write, none of a dropped ray
+    if (n < N) num_steps = lz_train_ray_emit(n, n, N, M, offsets, base, total, rays, xyzs, dirs, deltas, point_index);
+    lz_zero_sample_margins(n, base, total, M, xyzs, dirs, deltas);
     LzMarch m;
     const uint32_t nc = n < N ? n : N - 1;
-    m.init(rays_o + (size_t)nc * 3, rays_d + (size_t)nc * 3, bound, dt_gamma, max_steps, C, H, grid);
-    if (H <= LZ_MORTON_LUT) m.morton_lut = mlut;
-    const float far = fars[nc];
-    float t = nears[nc];
-    t = lz_fmaf(lz_clampf(t * dt_gamma, m.dt_min, m.dt_max), noises[nc], t);
+    float far, t = lz_march_train_start(m, rays_o, rays_d, nc, bound, dt_gamma, max_steps, C, H, grid, mlut, nears, fars, noises, far);
     sdir[wv][lane][0] = m.dx; sdir[wv][lane][1] = m.dy; sdir[wv][lane][2] = m.dz;
     srow[wv][lane] = point_index;
     uint32_t step = 0, nb = 0;
@@ -612,7 +577,7 @@ lz_k_march_train_write(const float* __restrict__ rays_o, const float* __restrict
     };
     float x, y, z, dt;
     for (;;) {
-        const bool can = active && t < far && step < num_steps;
+        const bool can = t < far && step < num_steps;
         if (!__ballot(can)) break;
         if (can && m.probe(t, x, y, z, dt)) {
             t += dt;
@@ -626,34 +591,14 @@ lz_k_march_train_write(const float* __restrict__ rays_o, const float* __restrict
     flush();
 }
 
-extern "C" int lz_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
-                                   uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
-                                   const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
-                                   const float* noises, void* workspace, lz_stream_t stream) {
-    LZ_REQUIRE(C >= 1 && C <= 8 && H > 0, LZ_ERR_BAD_ARGUMENT, "march_rays_train: cascade must be in [1, 8]");
-    if (N == 0) return LZ_OK;
-    LZ_REQUIRE(workspace, LZ_ERR_BAD_ARGUMENT, "march_rays_train: workspace of (N + 2) * 4 bytes required");
-    // noises is always a tensor (zeros without perturb, raymarching.py:226-229); with M == 0 the sample buffers are not written
-    LZ_REQUIRE(rays_o && rays_d && grid && nears && fars && rays && counter && noises, LZ_ERR_BAD_ARGUMENT, "march_rays_train: null tensor");
-    LZ_REQUIRE(M == 0 || (xyzs && dirs && deltas), LZ_ERR_BAD_ARGUMENT, "march_rays_train: null sample buffers with M > 0");
-    int* counts = reinterpret_cast<int*>(workspace);
-    int* base = counts + N;
-    hipStream_t st = lz_st(stream);
-    hipLaunchKernelGGL(lz_k_march_train_count, dim3(lz_div_up(N, 256)), dim3(256), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, noises, counts);
-    hipLaunchKernelGGL(lz_k_exclusive_scan_1wg, dim3(1), dim3(1024), 0, st, counts, N, counter, base);
-    hipLaunchKernelGGL(lz_k_march_train_write, dim3(lz_div_up(N, LZ_MT_WG)), dim3(LZ_MT_WG), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, noises, counts, counts, base, counter, xyzs, dirs, deltas, rays);
-    LZ_CHECK_LAUNCH("march_rays_train");
-    return LZ_OK;
-}
-
 __global__ void __launch_bounds__(256)
 lz_k_march_train_backward(const float* __restrict__ grad_xyzs, const float* __restrict__ grad_dirs, const int* __restrict__ rays,
                           const float* __restrict__ deltas, uint32_t N, uint32_t M, float* __restrict__ grad_rays_o,
                           float* __restrict__ grad_rays_d) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= N) return;
-    const uint32_t offset = (uint32_t)rays[(size_t)n * 3 + 1], num_steps = (uint32_t)rays[(size_t)n * 3 + 2];
-    if (num_steps == 0 || offset + num_steps > M) return;
+    const LzTrainRay ray = lz_train_ray(rays, n, N, M);
+    const uint32_t offset = ray.offset, num_steps = ray.ns();
+    if (num_steps == 0) return;
     float go[3], gd[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) { go[k] = grad_rays_o[(size_t)n * 3 + k]; gd[k] = grad_rays_d[(size_t)n * 3 + k]; }
@@ -696,22 +641,9 @@ extern "C" int lz_march_rays_train_backward(const float* grad_xyzs, const float*
 // fused frame kernel.  Measured on the cfg3 step (65 536 random rays, 5.99 M samples): light f16 forward 1.36 -> 0.71 ms, inference f16
 // head 1.31 -> 0.59 ms.  rays[i] = (ray id, o_i, c_i) with o_i the RAY-MAJOR offset (exclusive scan in processing order): the drop rule
 // (o_i + c_i > M, raymarching.cu:457) is unchanged and the dropped rays are a suffix, so a partly dropped group still fits its rows.
-// Compositing and the march's backward walk a group with one ballot per step: alive = ballot(k < c), row = o_g + S + popc(alive & lanes
-// below), S += popc(alive) -- loads and stores of consecutive lanes are consecutive rows.
-
-#ifndef LZ_TRAIN_GROUP
-#define LZ_TRAIN_GROUP 64       /* rays per group of the step-major layout: 16, 32 or 64 (lz_train_group_size()) */
-#endif
-static_assert(LZ_TRAIN_GROUP == 16 || LZ_TRAIN_GROUP == 32 || LZ_TRAIN_GROUP == 64, "group = 16, 32 or 64 lanes of a wave");
-// lanes of this lane's group / those of them below this lane
-__device__ __forceinline__ unsigned long long lz_tg_mask(uint32_t lane) {
-    return LZ_TRAIN_GROUP == 64 ? ~0ull : (((1ull << LZ_TRAIN_GROUP) - 1ull) << (lane & ~(uint32_t)(LZ_TRAIN_GROUP - 1)));
-}
-// the group's first row: rays[] offset of the group's first lane (that lane always holds a ray when any lane of the group does)
-__device__ __forceinline__ uint32_t lz_tg_base(uint32_t offset, uint32_t lane) {
-    if (LZ_TRAIN_GROUP == 64) return (uint32_t)__builtin_amdgcn_readfirstlane((int)offset);
-    return (uint32_t)__shfl((int)offset, (int)(lane & ~(uint32_t)(LZ_TRAIN_GROUP - 1)), 64);
-}
+// The march, its backward and the compositing backward walk a group with one ballot per step (LzGroupWalk, lz_composite_train.h): alive =
+// ballot(k < c), row = o_g + S + popc(alive & lanes below), S += popc(alive) -- loads and stores of consecutive lanes are consecutive
+// rows.  The compositing forward spells the same walk out: on the shared one it ran 95 -> 109 us.
 extern "C" int lz_train_group_size(void) { return LZ_TRAIN_GROUP; }
 
 // sort key of a ray: rays of one camera by direction (octahedral map, 12 + 12 bits, Morton-interleaved), cameras apart by 2 bits per axis
@@ -782,49 +714,64 @@ lz_k_march_train_write_grouped(const float* __restrict__ rays_o, const float* __
         rays[(size_t)ray_index * 3] = (int)n;
         rays[(size_t)ray_index * 3 + 1] = (int)point_index;
         rays[(size_t)ray_index * 3 + 2] = (int)num_steps;
-        if (num_steps != 0 && point_index + num_steps <= M) c = num_steps;      // else: nothing marched / dropped for lack of room (raymarching.cu:457)
+        if (num_steps != 0 && !lz_train_ray_dropped(point_index, num_steps, M)) c = num_steps;      // else: nothing marched / dropped for lack of room (raymarching.cu:457)
         else if (num_steps != 0)                                                // the first dropped ray clears what is left of the buffer
-            for (uint32_t r = point_index; r < M; r++) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) { xyzs[(size_t)r * 3 + k] = 0.0f; dirs[(size_t)r * 3 + k] = 0.0f; }
-                deltas[(size_t)r * 2] = 0.0f; deltas[(size_t)r * 2 + 1] = 0.0f;
-            }
+            for (uint32_t r = point_index; r < M; r++) lz_zero_sample_row(r, xyzs, dirs, deltas);
     }
     {   // rows in front of the step's first and behind its last: zero (see lz_k_march_train_write)
         const uint32_t first = (uint32_t)base[0] < M ? (uint32_t)base[0] : M, last = (uint32_t)total[0] < M ? (uint32_t)total[0] : M;
         const uint32_t nthreads = gridDim.x * blockDim.x, span = first + (M - last);
-        for (uint32_t q = i; q < span; q += nthreads) {
-            const uint32_t r = q < first ? q : last + (q - first);
-#pragma unroll
-            for (int k = 0; k < 3; k++) { xyzs[(size_t)r * 3 + k] = 0.0f; dirs[(size_t)r * 3 + k] = 0.0f; }
-            deltas[(size_t)r * 2] = 0.0f; deltas[(size_t)r * 2 + 1] = 0.0f;
-        }
+        for (uint32_t q = i; q < span; q += nthreads) lz_zero_sample_row(q < first ? q : last + (q - first), xyzs, dirs, deltas);
     }
-    const uint32_t gb = lz_tg_base(point_index, lane);
+    LzGroupWalk walk;
+    walk.start(point_index, lane);
     LzMarch m;
-    m.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, grid);
-    if (H <= LZ_MORTON_LUT) m.morton_lut = mlut;
-    const float far = fars[n];
-    float t = nears[n];
-    t = lz_fmaf(lz_clampf(t * dt_gamma, m.dt_min, m.dt_max), noises[n], t);
-    const unsigned long long gm = lz_tg_mask(lane), below = ((1ull << lane) - 1ull) & gm;
-    uint32_t S = 0;
+    float far, t = lz_march_train_start(m, rays_o, rays_d, n, bound, dt_gamma, max_steps, C, H, grid, mlut, nears, fars, noises, far);
     for (uint32_t k = 0;; k++) {
         const bool want = k < c;
-        const unsigned long long all = __ballot(want), alive = all & gm;
-        if (!all) break;
+        if (!walk.step(want)) break;
         if (want) {
             float x = 0.0f, y = 0.0f, z = 0.0f, dt = 0.0f;
             bool found = false;
             while (!found && t < far) found = m.probe(t, x, y, z, dt);
             t += dt;
-            const size_t row = (size_t)gb + S + (uint32_t)__popcll(alive & below);
+            const size_t row = walk.row();
             xyzs[row * 3] = x; xyzs[row * 3 + 1] = y; xyzs[row * 3 + 2] = z;
             dirs[row * 3] = m.dx; dirs[row * 3 + 1] = m.dy; dirs[row * 3 + 2] = m.dz;
             *reinterpret_cast<float2*>(deltas + row * 2) = make_float2(dt, t);
         }
-        S += (uint32_t)__popcll(alive);
+        walk.next();
     }
+}
+
+// count -> scan -> write for both layouts; `grouped`: step-major rows, the rays taken in `order` (null: in ray-id order)
+static int lz_march_train_launch(const char* name, bool grouped, const float* rays_o, const float* rays_d, const uint8_t* grid, float bound,
+                                 float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
+                                 const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
+                                 const float* noises, const int32_t* order, void* workspace, lz_stream_t stream) {
+    int* counts = reinterpret_cast<int*>(workspace);
+    int* base = counts + N;
+    hipStream_t st = lz_st(stream);
+    hipLaunchKernelGGL(lz_k_march_train_count, dim3(lz_div_up(N, 256)), dim3(256), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, noises, counts, order);
+    hipLaunchKernelGGL(lz_k_exclusive_scan_1wg, dim3(1), dim3(1024), 0, st, counts, N, counter, base);
+    if (grouped) hipLaunchKernelGGL(lz_k_march_train_write_grouped, dim3(lz_div_up(N, 256)), dim3(256), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, noises, counts, order, base, counter, xyzs, dirs, deltas, rays);
+    else hipLaunchKernelGGL(lz_k_march_train_write, dim3(lz_div_up(N, LZ_MT_WG)), dim3(LZ_MT_WG), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, noises, counts, base, counter, xyzs, dirs, deltas, rays);
+    LZ_CHECK_LAUNCH(name);
+    return LZ_OK;
+}
+
+extern "C" int lz_march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                                   uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
+                                   const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
+                                   const float* noises, void* workspace, lz_stream_t stream) {
+    LZ_REQUIRE(C >= 1 && C <= 8 && H > 0, LZ_ERR_BAD_ARGUMENT, "march_rays_train: cascade must be in [1, 8]");
+    if (N == 0) return LZ_OK;
+    LZ_REQUIRE(workspace, LZ_ERR_BAD_ARGUMENT, "march_rays_train: workspace of (N + 2) * 4 bytes required");
+    // noises is always a tensor (zeros without perturb, raymarching.py:226-229); with M == 0 the sample buffers are not written
+    LZ_REQUIRE(rays_o && rays_d && grid && nears && fars && rays && counter && noises, LZ_ERR_BAD_ARGUMENT, "march_rays_train: null tensor");
+    LZ_REQUIRE(M == 0 || (xyzs && dirs && deltas), LZ_ERR_BAD_ARGUMENT, "march_rays_train: null sample buffers with M > 0");
+    return lz_march_train_launch("march_rays_train", false, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas, rays,
+                                 counter, noises, nullptr, workspace, stream);
 }
 
 extern "C" int lz_march_rays_train_grouped(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
@@ -836,14 +783,8 @@ extern "C" int lz_march_rays_train_grouped(const float* rays_o, const float* ray
     LZ_REQUIRE(workspace, LZ_ERR_BAD_ARGUMENT, "march_rays_train_grouped: workspace of (N + 2) * 4 bytes required");
     LZ_REQUIRE(rays_o && rays_d && grid && nears && fars && rays && counter && noises, LZ_ERR_BAD_ARGUMENT, "march_rays_train_grouped: null tensor");
     LZ_REQUIRE(M == 0 || (xyzs && dirs && deltas), LZ_ERR_BAD_ARGUMENT, "march_rays_train_grouped: null sample buffers with M > 0");
-    int* counts = reinterpret_cast<int*>(workspace);
-    int* base = counts + N;
-    hipStream_t st = lz_st(stream);
-    hipLaunchKernelGGL(lz_k_march_train_count, dim3(lz_div_up(N, 256)), dim3(256), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, noises, counts, order);
-    hipLaunchKernelGGL(lz_k_exclusive_scan_1wg, dim3(1), dim3(1024), 0, st, counts, N, counter, base);
-    hipLaunchKernelGGL(lz_k_march_train_write_grouped, dim3(lz_div_up(N, 256)), dim3(256), 0, st, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, noises, counts, order, base, counter, xyzs, dirs, deltas, rays);
-    LZ_CHECK_LAUNCH("march_rays_train_grouped");
-    return LZ_OK;
+    return lz_march_train_launch("march_rays_train_grouped", true, rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas,
+                                 rays, counter, noises, order, workspace, stream);
 }
 
 __global__ void __launch_bounds__(64)
@@ -856,21 +797,19 @@ lz_k_march_train_backward_grouped(const float* __restrict__ grad_xyzs, const flo
         n = (uint32_t)rays[(size_t)i * 3];
         offset = (uint32_t)rays[(size_t)i * 3 + 1];
         c = (uint32_t)rays[(size_t)i * 3 + 2];
-        if (offset + c > M) c = 0;
+        if (lz_train_ray_dropped(offset, c, M)) c = 0;
     }
-    const uint32_t gb = lz_tg_base(offset, lane);
+    LzGroupWalk walk;
+    walk.start(offset, lane);
     float go[3] = {0, 0, 0}, gd[3] = {0, 0, 0};
     if (c > 0)
 #pragma unroll
         for (int k = 0; k < 3; k++) { go[k] = grad_rays_o[(size_t)n * 3 + k]; gd[k] = grad_rays_d[(size_t)n * 3 + k]; }
-    const unsigned long long gm = lz_tg_mask(lane), below = ((1ull << lane) - 1ull) & gm;
-    uint32_t S = 0;
     for (uint32_t s = 0;; s++) {
         const bool want = s < c;
-        const unsigned long long all = __ballot(want), alive = all & gm;
-        if (!all) break;
+        if (!walk.step(want)) break;
         if (want) {
-            const size_t row = (size_t)gb + S + (uint32_t)__popcll(alive & below);
+            const size_t row = walk.row();
             const float tt = deltas[row * 2 + 1];
 #pragma unroll
             for (int k = 0; k < 3; k++) {
@@ -879,7 +818,7 @@ lz_k_march_train_backward_grouped(const float* __restrict__ grad_xyzs, const flo
                 gd[k] += lz_fmaf(gx, tt, grad_dirs[row * 3 + k]);
             }
         }
-        S += (uint32_t)__popcll(alive);
+        walk.next();
     }
     if (c > 0)
 #pragma unroll
@@ -1062,15 +1001,9 @@ lz_k_composite_train_fwd(const float* __restrict__ sigmas, const float* __restri
     constexpr int ROW = LZ_CT_FWD_NF * 64 + 1;
     __shared__ float st[LZ_CT_CHUNK * ROW];
     const uint32_t lane = threadIdx.x, n = blockIdx.x * 64 + lane;
-    const bool have = n < N;
-    uint32_t index = 0, offset = 0, ns = 0;
-    if (have) {
-        index = (uint32_t)rays[(size_t)n * 3];
-        offset = (uint32_t)rays[(size_t)n * 3 + 1];
-        ns = (uint32_t)rays[(size_t)n * 3 + 2];
-        if (ns == 0 || offset + ns > M) ns = 0;   // dropped ray (raymarching.cu:1905): zero outputs
-    }
-    float T = 1.0f, r = 0, g = 0, b = 0, ws = 0, d = 0, a0 = 0, a1 = 0, u = 0;
+    const LzTrainRay ray = lz_train_ray(rays, n, N, M);
+    const uint32_t offset = ray.offset, ns = ray.ns();      // a dropped ray (raymarching.cu:1905): zero outputs
+    LzCompositeFwd<NAMB, AMBW, UNC> acc;
     bool live = ns > 0;
     const uint32_t sub = lane >> 3, j = lane & 7;
     for (uint32_t base = 0; __any(live && base < ns); base += LZ_CT_CHUNK) {
@@ -1099,29 +1032,14 @@ lz_k_composite_train_fwd(const float* __restrict__ sigmas, const float* __restri
         for (uint32_t k = 0; k < LZ_CT_CHUNK; k++) {
             if (live && base + k < ns) {
                 const float* src = st + k * ROW + lane;
-                const float alpha = 1.0f - lz_expf(-src[0] * src[64]);
-                const float weight = alpha * T;
-                r = lz_fmaf(weight, src[192], r);
-                g = lz_fmaf(weight, src[256], g);
-                b = lz_fmaf(weight, src[320], b);
-                d = lz_fmaf(weight, src[128], d);
-                ws += weight;
-                if (NAMB > 0) a0 = AMBW ? lz_fmaf(weight, src[384], a0) : a0 + src[384];
-                if (NAMB > 1) a1 = AMBW ? lz_fmaf(weight, src[448], a1) : a1 + src[448];
-                if (UNC) u = lz_fmaf(weight, src[512], u);
-                T *= 1.0f - alpha;
-                if (T < T_thresh) live = false;
+                acc.step(src[0], src[64], src[128], src[192], src[256], src[320], NAMB > 0 ? src[384] : 0.0f, NAMB > 1 ? src[448] : 0.0f,
+                         UNC ? src[512] : 0.0f);
+                live = !(acc.T < T_thresh);
             }
         }
         __syncthreads();
     }
-    if (!have) return;
-    weights_sum[index] = ws;
-    if (NAMB > 0) amb0_sum[index] = a0;
-    if (NAMB > 1) amb1_sum[index] = a1;
-    if (UNC) unc_sum[index] = u;
-    depth[index] = d;
-    image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
+    if (n < N) acc.store(ray.index, weights_sum, amb0_sum, amb1_sum, unc_sum, depth, image);
 }
 
 template <int NAMB, bool AMBW, bool UNC>
@@ -1137,28 +1055,11 @@ lz_k_composite_train_bwd(const float* __restrict__ grad_weights_sum, const float
     constexpr int ROW = LZ_CT_BWD_NF * 64 + 1, ROWO = LZ_CT_BWD_NO * 64 + 1;
     __shared__ float st[LZ_CT_CHUNK * ROW];
     __shared__ float so[LZ_CT_CHUNK * ROWO];
-    const uint32_t lane = threadIdx.x, n = blockIdx.x * 64 + lane;
-    uint32_t index = 0, offset = 0, ns = 0;
-    if (n < N) {
-        index = (uint32_t)rays[(size_t)n * 3];
-        offset = (uint32_t)rays[(size_t)n * 3 + 1];
-        ns = (uint32_t)rays[(size_t)n * 3 + 2];
-        if (ns == 0 || offset + ns > M) ns = 0;   // dropped ray: its gradients stay as the caller initialised them
-    }
-    float gi0 = 0, gi1 = 0, gi2 = 0, gws = 0, ga0 = 0, ga1 = 0, gu = 0, r_final = 0, g_final = 0, b_final = 0, ws_final = 0, amb_final = 0,
-          unc_final = 0;
-    if (ns > 0) {
-        gi0 = grad_image[(size_t)index * 3]; gi1 = grad_image[(size_t)index * 3 + 1]; gi2 = grad_image[(size_t)index * 3 + 2];
-        gws = grad_weights_sum[index];
-        if (NAMB > 0) ga0 = grad_amb0_sum[index];
-        if (NAMB > 1) ga1 = grad_amb1_sum[index];
-        if (UNC) gu = grad_unc_sum[index];
-        r_final = image[(size_t)index * 3]; g_final = image[(size_t)index * 3 + 1]; b_final = image[(size_t)index * 3 + 2];
-        ws_final = weights_sum[index];
-        if (NAMB > 0 && AMBW) amb_final = amb0_sum[index];
-        if (UNC) unc_final = unc_sum[index];
-    }
-    float T = 1.0f, r = 0, g = 0, b = 0, ws = 0, amb = 0, u = 0;
+    const uint32_t lane = threadIdx.x;
+    const LzTrainRay ray = lz_train_ray(rays, blockIdx.x * 64 + lane, N, M);
+    const uint32_t offset = ray.offset, ns = ray.ns();      // a dropped ray: its gradients stay as the caller initialised them
+    LzCompositeBwd<NAMB, AMBW, UNC> acc;
+    if (ns > 0) acc.load(ray.index, grad_weights_sum, grad_amb0_sum, grad_amb1_sum, grad_unc_sum, grad_image, weights_sum, amb0_sum, unc_sum, image);
     bool live = ns > 0;
     const uint32_t sub = lane >> 3, j = lane & 7;
     for (uint32_t base = 0; __any(live && base < ns); base += LZ_CT_CHUNK) {
@@ -1186,32 +1087,16 @@ lz_k_composite_train_bwd(const float* __restrict__ grad_weights_sum, const float
             if (live && base + k < ns) {
                 const float* src = st + k * ROW + lane;
                 float* out = so + k * ROWO + lane;
-                const float dl0 = src[64], c0 = src[128], c1 = src[192], c2 = src[256];
-                const float alpha = 1.0f - lz_expf(-src[0] * dl0);
-                const float weight = alpha * T;
-                r = lz_fmaf(weight, c0, r);
-                g = lz_fmaf(weight, c1, g);
-                b = lz_fmaf(weight, c2, b);
-                float av = 0.0f, uv = 0.0f;
-                if (NAMB > 0 && AMBW) { av = src[320]; amb = lz_fmaf(weight, av, amb); }
-                if (UNC) { uv = src[384]; u = lz_fmaf(weight, uv, u); }
-                ws += weight;
-                T *= 1.0f - alpha;
-                out[64] = gi0 * weight;
-                out[128] = gi1 * weight;
-                out[192] = gi2 * weight;
-                if (NAMB > 0) out[256] = AMBW ? ga0 * weight : ga0;
-                if (NAMB > 1) out[320] = ga1;
-                if (UNC) out[384] = gu * weight;
-                float s = gi0 * lz_fmaf(T, c0, -(r_final - r));
-                s = lz_fmaf(gi1, lz_fmaf(T, c1, -(g_final - g)), s);
-                s = lz_fmaf(gi2, lz_fmaf(T, c2, -(b_final - b)), s);
-                if (NAMB > 0 && AMBW) s = lz_fmaf(ga0, lz_fmaf(T, av, -(amb_final - amb)), s);
-                if (UNC) s = lz_fmaf(gu, lz_fmaf(T, uv, -(unc_final - u)), s);
-                s = lz_fmaf(gws, 1 - ws_final, s);
-                out[0] = dl0 * s;
+                const auto gr = acc.step(src[0], src[64], src[128], src[192], src[256], (NAMB > 0 && AMBW) ? src[320] : 0.0f, UNC ? src[384] : 0.0f);
+                out[0] = gr.sigma;
+                out[64] = acc.gi0 * gr.weight;
+                out[128] = acc.gi1 * gr.weight;
+                out[192] = acc.gi2 * gr.weight;
+                if (NAMB > 0) out[256] = AMBW ? acc.ga0 * gr.weight : acc.ga0;
+                if (NAMB > 1) out[320] = acc.ga1;
+                if (UNC) out[384] = acc.gu * gr.weight;
                 done = k + 1;
-                if (T < T_thresh) live = false;
+                live = !(acc.T < T_thresh);
             }
         }
         __syncthreads();
@@ -1237,7 +1122,8 @@ lz_k_composite_train_bwd(const float* __restrict__ grad_weights_sum, const float
 
 // compositing over the STEP-MAJOR layout (see lz_k_march_train_write_grouped): lane j = ray 64 g + j of rays[]; per step one ballot gives
 // every lane its row, the loads of a step are consecutive rows across the lanes (no LDS transposition), eight steps are fetched ahead of
-// the sequential T chain.  Same arithmetic in the same order as the ray-major kernels above.
+// the sequential T chain.  Same arithmetic in the same order as the ray-major kernels above (LzCompositeFwd / LzCompositeBwd), written out
+// here: on the shared accumulators these two kernels ran 96 -> 143 us and 125 -> 130 us.
 template <int NAMB, bool AMBW, bool UNC>
 __global__ void __launch_bounds__(64)
 lz_k_composite_train_fwd_g(const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ amb0,
@@ -1252,7 +1138,7 @@ lz_k_composite_train_fwd_g(const float* __restrict__ sigmas, const float* __rest
         index = (uint32_t)rays[(size_t)n * 3];
         offset = (uint32_t)rays[(size_t)n * 3 + 1];
         ns = (uint32_t)rays[(size_t)n * 3 + 2];
-        if (ns == 0 || offset + ns > M) ns = 0;   // dropped ray (raymarching.cu:1905): zero outputs
+        if (ns == 0 || lz_train_ray_dropped(offset, ns, M)) ns = 0;   // dropped ray (raymarching.cu:1905): zero outputs
     }
     const uint32_t gb = lz_tg_base(offset, lane);
     const unsigned long long gm = lz_tg_mask(lane), below = ((1ull << lane) - 1ull) & gm;
@@ -1322,22 +1208,16 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
     // or a dropped one as well, and a lane carries one (zb, ze) range for those.  No trip at base 0, the training step's.
     if (blockIdx.x == 0) {
         const uint32_t first = (uint32_t)rays[1], head = first < M ? first : M;
-        for (size_t i = lane; i < head; i += 64) {
-            grad_sigmas[i] = 0.0f;
-            grad_rgbs[i * 3] = 0.0f; grad_rgbs[i * 3 + 1] = 0.0f; grad_rgbs[i * 3 + 2] = 0.0f;
-            if (NAMB > 0) grad_amb0[i] = 0.0f;
-            if (NAMB > 1) grad_amb1[i] = 0.0f;
-            if (UNC) grad_unc[i] = 0.0f;
-        }
+        for (size_t i = lane; i < head; i += 64) lz_zero_grad_row<NAMB, UNC>(i, grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc);
     }
     uint32_t zb = 0, ze = 0;
     if (n < N) {
         index = (uint32_t)rays[(size_t)n * 3];
         offset = (uint32_t)rays[(size_t)n * 3 + 1];
         ns = (uint32_t)rays[(size_t)n * 3 + 2];
-        const bool dropped = offset + ns > M;
+        const bool dropped = lz_train_ray_dropped(offset, ns, M);
         if (dropped) {              // the dropped rays are a suffix: the first of them clears everything from its offset on
-            const bool prev_kept = n == 0 || (uint32_t)rays[(size_t)(n - 1) * 3 + 1] + (uint32_t)rays[(size_t)(n - 1) * 3 + 2] <= M;
+            const bool prev_kept = n == 0 || !lz_train_ray_dropped((uint32_t)rays[(size_t)(n - 1) * 3 + 1], (uint32_t)rays[(size_t)(n - 1) * 3 + 2], M);
             if (prev_kept && offset < M) { zb = offset; ze = M; }
         } else if (n == N - 1 && offset + ns < M) { zb = offset + ns; ze = M; }
         if (ns == 0 || dropped) ns = 0;
@@ -1345,16 +1225,10 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
     for (unsigned long long todo = __ballot(zb < ze); todo; todo &= todo - 1ull) {
         const int src = __builtin_ctzll(todo);
         const uint32_t r0 = (uint32_t)__shfl((int)zb, src, 64), r1 = (uint32_t)__shfl((int)ze, src, 64);
-        for (size_t i = (size_t)r0 + lane; i < r1; i += 64) {
-            grad_sigmas[i] = 0.0f;
-            grad_rgbs[i * 3] = 0.0f; grad_rgbs[i * 3 + 1] = 0.0f; grad_rgbs[i * 3 + 2] = 0.0f;
-            if (NAMB > 0) grad_amb0[i] = 0.0f;
-            if (NAMB > 1) grad_amb1[i] = 0.0f;
-            if (UNC) grad_unc[i] = 0.0f;
-        }
+        for (size_t i = (size_t)r0 + lane; i < r1; i += 64) lz_zero_grad_row<NAMB, UNC>(i, grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc);
     }
-    const uint32_t gb = lz_tg_base(offset, lane);
-    const unsigned long long gm = lz_tg_mask(lane), below = ((1ull << lane) - 1ull) & gm;
+    LzGroupWalk walk;
+    walk.start(offset, lane);
     float gi0 = 0, gi1 = 0, gi2 = 0, gws = 0, ga0 = 0, ga1 = 0, gu = 0, r_final = 0, g_final = 0, b_final = 0, ws_final = 0, amb_final = 0,
           unc_final = 0;
     if (ns > 0) {
@@ -1370,15 +1244,14 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
     }
     float T = 1.0f, r = 0, g = 0, b = 0, ws = 0, amb = 0, u = 0;
     bool live = ns > 0;
-    uint32_t S = 0;
     for (uint32_t base = 0; __any(base < ns); base += LZ_CT_CHUNK) {        // to the end of the longest ray: the rows behind a termination are zeroed
         float v[LZ_CT_CHUNK][LZ_CT_BWD_NF];
         uint32_t row[LZ_CT_CHUNK];
 #pragma unroll
         for (uint32_t k = 0; k < LZ_CT_CHUNK; k++) {
             const bool has = base + k < ns;
-            const unsigned long long alive = __ballot(has) & gm;
-            row[k] = gb + S + (uint32_t)__popcll(alive & below);
+            walk.step(has);
+            row[k] = (uint32_t)walk.row();
             if (has && live) {
                 const size_t i = row[k];
                 v[k][0] = sigmas[i]; v[k][1] = deltas[i * 2];
@@ -1386,7 +1259,7 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
                 if (NAMB > 0 && AMBW) v[k][5] = amb0[i];
                 if (UNC) v[k][6] = unc[i];
             }
-            S += (uint32_t)__popcll(alive);
+            walk.next();
         }
 #pragma unroll
         for (uint32_t k = 0; k < LZ_CT_CHUNK; k++) {
@@ -1417,14 +1290,7 @@ lz_k_composite_train_bwd_g(const float* __restrict__ grad_weights_sum, const flo
                 s = lz_fmaf(gws, 1 - ws_final, s);
                 grad_sigmas[i] = dl0 * s;
                 if (T < T_thresh) live = false;
-            } else if (base + k < ns) {
-                const size_t i = row[k];
-                grad_sigmas[i] = 0.0f;
-                grad_rgbs[i * 3] = 0.0f; grad_rgbs[i * 3 + 1] = 0.0f; grad_rgbs[i * 3 + 2] = 0.0f;
-                if (NAMB > 0) grad_amb0[i] = 0.0f;
-                if (NAMB > 1) grad_amb1[i] = 0.0f;
-                if (UNC) grad_unc[i] = 0.0f;
-            }
+            } else if (base + k < ns) lz_zero_grad_row<NAMB, UNC>(row[k], grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc);
         }
     }
 }
@@ -1501,6 +1367,9 @@ lz_k_composite_rays(uint32_t n_alive_h, uint32_t n_step_h, const lz_loop_state* 
     }
 }
 
+// the kernel of a training compositing entry for its `layout`: KERNEL (ray-major rows) or KERNEL_g (step-major groups)
+#define LZ_LAYOUT_KERNEL(KERNEL, NA, AW, HU) (layout == 1 ? KERNEL##_g<NA, AW, HU> : KERNEL<NA, AW, HU>)
+
 // (n_amb, amb_weighted, has_unc) -> template instance
 #define LZ_VARIANT_SWITCH(n_amb, aw, hu, CALL)                                     \
     do {                                                                           \
@@ -1525,11 +1394,7 @@ extern "C" int lz_composite_train_forward_v(const float* sigmas, const float* rg
     if (N == 0) return LZ_OK;
     dim3 grid(lz_div_up(N, 64)), block(64);   // one wave per workgroup (wave-local barriers)
     hipStream_t st = lz_st(stream);
-#define CALL(NA, AW, HU)                                                                                                             \
-    do {                                                                                                                             \
-        if (layout == 1) hipLaunchKernelGGL((lz_k_composite_train_fwd_g<NA, AW, HU>), grid, block, 0, st, sigmas, rgbs, amb0, amb1, unc, deltas, rays, M, N, T_thresh, weights_sum, amb0_sum, amb1_sum, unc_sum, depth, image); \
-        else hipLaunchKernelGGL((lz_k_composite_train_fwd<NA, AW, HU>), grid, block, 0, st, sigmas, rgbs, amb0, amb1, unc, deltas, rays, M, N, T_thresh, weights_sum, amb0_sum, amb1_sum, unc_sum, depth, image); \
-    } while (0)
+#define CALL(NA, AW, HU) hipLaunchKernelGGL(LZ_LAYOUT_KERNEL(lz_k_composite_train_fwd, NA, AW, HU), grid, block, 0, st, sigmas, rgbs, amb0, amb1, unc, deltas, rays, M, N, T_thresh, weights_sum, amb0_sum, amb1_sum, unc_sum, depth, image)
     LZ_VARIANT_SWITCH(n_amb, amb_weighted, has_unc, CALL);
 #undef CALL
     LZ_CHECK_LAUNCH("composite_rays_train_forward");
@@ -1555,11 +1420,7 @@ extern "C" int lz_composite_train_backward_v(const float* grad_weights_sum, cons
     if (N == 0) return LZ_OK;
     dim3 grid(lz_div_up(N, 64)), block(64);
     hipStream_t st = lz_st(stream);
-#define CALL(NA, AW, HU)                                                                                                             \
-    do {                                                                                                                             \
-        if (layout == 1) hipLaunchKernelGGL((lz_k_composite_train_bwd_g<NA, AW, HU>), grid, block, 0, st, grad_weights_sum, grad_amb0_sum, grad_amb1_sum, grad_unc_sum, grad_image, sigmas, rgbs, amb0, unc, deltas, rays, weights_sum, amb0_sum, unc_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc); \
-        else hipLaunchKernelGGL((lz_k_composite_train_bwd<NA, AW, HU>), grid, block, 0, st, grad_weights_sum, grad_amb0_sum, grad_amb1_sum, grad_unc_sum, grad_image, sigmas, rgbs, amb0, unc, deltas, rays, weights_sum, amb0_sum, unc_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc); \
-    } while (0)
+#define CALL(NA, AW, HU) hipLaunchKernelGGL(LZ_LAYOUT_KERNEL(lz_k_composite_train_bwd, NA, AW, HU), grid, block, 0, st, grad_weights_sum, grad_amb0_sum, grad_amb1_sum, grad_unc_sum, grad_image, sigmas, rgbs, amb0, unc, deltas, rays, weights_sum, amb0_sum, unc_sum, image, M, N, T_thresh, grad_sigmas, grad_rgbs, grad_amb0, grad_amb1, grad_unc)
     LZ_VARIANT_SWITCH(n_amb, amb_weighted, has_unc, CALL);
 #undef CALL
     LZ_CHECK_LAUNCH("composite_rays_train_backward");

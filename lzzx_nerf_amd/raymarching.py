@@ -272,90 +272,58 @@ def _composite_train_bwd(variant, g_ws, g_a0, g_a1, g_u, g_img, sigmas, rgbs, am
     return grad_sigmas, grad_rgbs, ga0, ga1, gu
 
 
-def _make_train_1amb(variant):
-    """composite_rays_train (ambient unweighted) / composite_rays_train_sigma (ambient weighted): raymarching.py:283-341, 442-500"""
+def _make_composite_train(variant, channels):
+    """The training compositing Function of a kernel variant (n_amb, amb_weighted, has_unc): forward(sigmas, rgbs, *channels, deltas, rays,
+    T_thresh=1e-4) -> (weights_sum, one sum per channel, depth, image).  `channels` names the ambient inputs and then the uncertainty
+    input, in the reference's argument order."""
+    na, _, hu = variant
+    nc = len(channels)
+    assert nc == na + hu
+
+    def slots(c):   # one value per channel -> the kernels' (amb0, amb1, unc)
+        c = tuple(c)
+        return c[:na] + (None,) * (2 - na) + (c[na:] or (None,))
 
     class _Fn(Function):
         @staticmethod
         @_fwd32
-        def forward(ctx, sigmas, rgbs, ambient, deltas, rays, T_thresh=1e-4):
-            sigmas, rgbs, ambient = sigmas.contiguous(), rgbs.contiguous(), ambient.contiguous()
-            deltas = deltas.contiguous()
+        def forward(ctx, sigmas, rgbs, *rest):
+            if not nc + 2 <= len(rest) <= nc + 3:
+                raise TypeError(f"expected (sigmas, rgbs, {', '.join(channels)}, deltas, rays[, T_thresh]), got {2 + len(rest)} arguments")
+            sigmas, rgbs, deltas = sigmas.contiguous(), rgbs.contiguous(), rest[nc].contiguous()
+            chans, rays = tuple(t.contiguous() for t in rest[:nc]), rest[nc + 1]
+            T_thresh = rest[nc + 2] if len(rest) > nc + 2 else 1e-4
             ctx.layout = _layout_of(rays)
-            ws, a0s, _, _, depth, image = _composite_train_fwd(variant, sigmas, rgbs, ambient, None, None, deltas, rays, T_thresh, ctx.layout)
-            ctx.save_for_backward(sigmas, rgbs, ambient, deltas, rays, ws, a0s, depth, image)
+            ws, a0s, a1s, us, depth, image = _composite_train_fwd(variant, sigmas, rgbs, *slots(chans), deltas, rays, T_thresh, ctx.layout)
+            sums = tuple(t for t in (a0s, a1s, us) if t is not None)
+            ctx.save_for_backward(sigmas, rgbs, *chans, deltas, rays, ws, *sums, depth, image)
             ctx.T_thresh = T_thresh
-            return ws, a0s, depth, image
+            return (ws,) + sums + (depth, image)
 
         @staticmethod
         @_bwd
-        def backward(ctx, grad_weights_sum, grad_ambient_sum, grad_depth, grad_image):
-            # grad_depth is not propagated (raymarching.py:323)
-            sigmas, rgbs, ambient, deltas, rays, ws, a0s, depth, image = ctx.saved_tensors
-            gs, gr, ga, _, _ = _composite_train_bwd(variant, grad_weights_sum.contiguous(), grad_ambient_sum.contiguous(), None, None,
-                                                   grad_image.contiguous(), sigmas, rgbs, ambient, None, None, deltas, rays, ws, a0s,
-                                                   None, image, ctx.T_thresh, ctx.layout)
-            return gs, gr, ga, None, None, None
+        def backward(ctx, grad_weights_sum, *grads):
+            # grads: one per channel sum, then grad_depth (not propagated, raymarching.py:323) and grad_image
+            grad_sums, grad_image = [g.contiguous() for g in grads[:nc]], grads[nc + 1].contiguous()
+            # saved: sigmas, rgbs, the nc channels, deltas, rays, weights_sum, the nc channel sums, depth, image
+            saved = list(ctx.saved_tensors)
+            sigmas, rgbs = saved[:2]
+            chans, sums = saved[2:2 + nc], saved[5 + nc:5 + 2 * nc]
+            deltas, rays, weights_sum = saved[2 + nc:5 + nc]
+            image = saved[-1]
+            amb0_sum, _, unc_sum = slots(sums)
+            grad_sigmas, grad_rgbs, *grad_chans = _composite_train_bwd(
+                variant, grad_weights_sum.contiguous(), *slots(grad_sums), grad_image, sigmas, rgbs, *slots(chans), deltas, rays,
+                weights_sum, amb0_sum, unc_sum, image, ctx.T_thresh, ctx.layout)
+            return (grad_sigmas, grad_rgbs, *(g for g in grad_chans if g is not None), None, None, None)   # ..., deltas, rays, T_thresh
 
     return _Fn
 
 
-_composite_rays_train = _make_train_1amb((1, 0, 0))
-composite_rays_train = _composite_rays_train.apply
-_composite_rays_train_sigma = _make_train_1amb((1, 1, 0))
-composite_rays_train_sigma = _composite_rays_train_sigma.apply
-
-
-class _composite_rays_train_uncertainty(Function):  # raymarching.py:516-578
-    @staticmethod
-    @_fwd32
-    def forward(ctx, sigmas, rgbs, ambient, uncertainty, deltas, rays, T_thresh=1e-4):
-        sigmas, rgbs, ambient, uncertainty = sigmas.contiguous(), rgbs.contiguous(), ambient.contiguous(), uncertainty.contiguous()
-        deltas = deltas.contiguous()
-        ctx.layout = _layout_of(rays)
-        ws, a0s, _, us, depth, image = _composite_train_fwd((1, 0, 1), sigmas, rgbs, ambient, None, uncertainty, deltas, rays, T_thresh, ctx.layout)
-        ctx.save_for_backward(sigmas, rgbs, ambient, uncertainty, deltas, rays, ws, a0s, us, depth, image)
-        ctx.T_thresh = T_thresh
-        return ws, a0s, us, depth, image
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, grad_weights_sum, grad_ambient_sum, grad_uncertainty_sum, grad_depth, grad_image):
-        sigmas, rgbs, ambient, uncertainty, deltas, rays, ws, a0s, us, depth, image = ctx.saved_tensors
-        gs, gr, ga, _, gu = _composite_train_bwd((1, 0, 1), grad_weights_sum.contiguous(), grad_ambient_sum.contiguous(), None,
-                                                 grad_uncertainty_sum.contiguous(), grad_image.contiguous(), sigmas, rgbs, ambient, None,
-                                                 uncertainty, deltas, rays, ws, a0s, us, image, ctx.T_thresh, ctx.layout)
-        return gs, gr, ga, gu, None, None, None
-
-
-composite_rays_train_uncertainty = _composite_rays_train_uncertainty.apply
-
-
-class _composite_rays_train_triplane(Function):  # raymarching.py:594-660
-    @staticmethod
-    @_fwd32
-    def forward(ctx, sigmas, rgbs, amb_aud, amb_eye, uncertainty, deltas, rays, T_thresh=1e-4):
-        sigmas, rgbs = sigmas.contiguous(), rgbs.contiguous()
-        amb_aud, amb_eye, uncertainty = amb_aud.contiguous(), amb_eye.contiguous(), uncertainty.contiguous()
-        deltas = deltas.contiguous()
-        ctx.layout = _layout_of(rays)
-        ws, a0s, a1s, us, depth, image = _composite_train_fwd((2, 0, 1), sigmas, rgbs, amb_aud, amb_eye, uncertainty, deltas, rays, T_thresh, ctx.layout)
-        ctx.save_for_backward(sigmas, rgbs, amb_aud, amb_eye, uncertainty, deltas, rays, ws, a0s, a1s, us, depth, image)
-        ctx.T_thresh = T_thresh
-        return ws, a0s, a1s, us, depth, image
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, grad_weights_sum, grad_amb_aud_sum, grad_amb_eye_sum, grad_uncertainty_sum, grad_depth, grad_image):
-        sigmas, rgbs, amb_aud, amb_eye, uncertainty, deltas, rays, ws, a0s, a1s, us, depth, image = ctx.saved_tensors
-        gs, gr, ga0, ga1, gu = _composite_train_bwd((2, 0, 1), grad_weights_sum.contiguous(), grad_amb_aud_sum.contiguous(),
-                                                    grad_amb_eye_sum.contiguous(), grad_uncertainty_sum.contiguous(),
-                                                    grad_image.contiguous(), sigmas, rgbs, amb_aud, amb_eye, uncertainty, deltas, rays,
-                                                    ws, a0s, us, image, ctx.T_thresh, ctx.layout)
-        return gs, gr, ga0, ga1, gu, None, None, None
-
-
-composite_rays_train_triplane = _composite_rays_train_triplane.apply
+composite_rays_train = _make_composite_train((1, 0, 0), ("ambient",)).apply                                # raymarching.py:283-341
+composite_rays_train_sigma = _make_composite_train((1, 1, 0), ("ambient",)).apply                          # raymarching.py:442-500
+composite_rays_train_uncertainty = _make_composite_train((1, 0, 1), ("ambient", "uncertainty")).apply      # raymarching.py:516-578
+composite_rays_train_triplane = _make_composite_train((2, 0, 1), ("amb_aud", "amb_eye", "uncertainty")).apply     # :594-660
 
 
 # ----------------------------------------

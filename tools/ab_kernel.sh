@@ -7,6 +7,6 @@ for v in $VARS; do
   python3 - <<PY
 import csv
 for r in csv.DictReader(open("gpurun_out/abk_${v}_kernel_stats.csv")):
-    if "$PAT" in r["Name"]: print("$v", r["Name"][:40], "avg %.1f min %.1f max %.1f us" % (float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3))
+    if "$PAT" in r["Name"]: print("$v", r["Name"][:40], "avg %.1f min %.1f max %.1f us" % (float(r["MeanSteadyNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3))
 PY
 done
