@@ -323,6 +323,9 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
     if (ph2 && F.state[LZF_P_SIZE] <= 0) return;
     typename HD::Ctx ctx;
     HD::stage(P, lds, q, ctx);
+    // the second-dispatched half of the workgroup (dispatch order inside a workgroup is not guaranteed; in practice it is the wave order)
+    const bool young = LZF_PRIO_YOUNG != 0 && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= LZF_WAVES / 2;
+    if constexpr (PREC != 1) ctx.young = young;
     float* slot = lds + HD::LDS_WORDS + wave * NF * NS;      // this wave's slots: slot[field * 16 + s]
     int* sloti = reinterpret_cast<int*>(slot);
     int* wg_stat = reinterpret_cast<int*>(lds + HD::LDS_WORDS + SLOT_WORDS);   // [0] samples, [1] slices, [2] waves done
@@ -352,7 +355,8 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
     if constexpr (S > 1) {
         const int j = s % S, lead = s - j;              // slot s = step j of the ray whose state sits at slot `lead`
         for (;;) {
-            if constexpr (PREC != 1 || LZ_F16W_PRIO != 0) __builtin_amdgcn_s_setprio(2);   // see the S = 1 loop
+            if constexpr (PREC != 1) lz_wave_prio(true, young);                            // see the S = 1 loop
+            else if constexpr (LZ_F16W_PRIO != 0) __builtin_amdgcn_s_setprio(2);
             // ---------------- refill + march (group leaders): up to S samples per ray into the staging fields ----------------
             const bool leader = slot_lane && j == 0;
             int ray = leader ? sloti[SF_RAY * NS + s] : -1;
@@ -558,7 +562,9 @@ lz_k_frame(typename LzfHead<PREC>::Args P, LzFrameK F) {
         for (;;) {
             // f32 heads: refill, march and the gather's address work run at a raised wave priority and the slice drops it once its loads are
             // issued (lz_head_gather<YIELD>): a wave that is about to wait on memory gets there first, the matrix phases fill the time
-            if constexpr (PREC != 1 || LZ_F16W_PRIO != 0) __builtin_amdgcn_s_setprio(2);
+            // (lz_wave_prio, lz_head_gather.h: what else runs raised -- LZF_PRIO_TAIL -- and the younger half's base -- LZF_PRIO_YOUNG)
+            if constexpr (PREC != 1) lz_wave_prio(true, young);
+            else if constexpr (LZ_F16W_PRIO != 0) __builtin_amdgcn_s_setprio(2);
             // ---------------- refill + march: every slot ends with a sample, crossing empty space, or empty with the queue dry ----------------
             int ray = slot_lane ? sloti[SF_RAY * NS + sl] : -1;
             bool have = false;

@@ -116,9 +116,45 @@ __device__ __forceinline__ void lz_head_map01(float px, float py, float pz, floa
     }
 }
 
+// Wave priorities of the fused f32 frame kernels (lz_frame.hip; the f16 kernels set their own).  A wave runs its sections either at its
+// base priority or RAISED, one above it.  LZF_PRIO_YOUNG = 0: base 0, raised 2 for every wave.  LZF_PRIO_YOUNG = 1: the second-dispatched
+// half of the workgroup (`young`, wave-uniform and in a scalar register: s_setprio ignores EXEC) has base 1 and raised 2, the first half
+// base 0 and raised 1 -- the static-priority form for the half that loses issue arbitration by age.
+// LZF_PRIO_TAIL = 1 also raises the vector-only phases behind the loads: the gather's interpolation, the slice's tail from the ind_code
+// k-step on, and with it the compositing (the raise holds until the next pass's gather has issued its loads), so that they finish in dense
+// bursts instead of being dealt out among another wave's MFMAs.  Both are A/B switches, 0 restores the kernel without them; what the A/B
+// found is in DESIGN 4.1 and profiles/r8_wave_phases_ab.json.
+#ifdef LZF_F16_TU       // the f16 frame kernels' compilation (lz_frame.hip): their priorities stay as they are
+#undef LZF_PRIO_TAIL
+#undef LZF_PRIO_YOUNG
+#define LZF_PRIO_TAIL 0
+#define LZF_PRIO_YOUNG 0
+#endif
+#ifndef LZF_PRIO_TAIL
+#define LZF_PRIO_TAIL 0
+#endif
+#ifndef LZF_PRIO_YOUNG
+#define LZF_PRIO_YOUNG 0
+#endif
+__device__ __forceinline__ void lz_wave_prio(bool raised, bool young) {
+#if LZF_PRIO_YOUNG
+    if (young) {
+        if (raised) __builtin_amdgcn_s_setprio(2);
+        else __builtin_amdgcn_s_setprio(1);
+    } else {
+        if (raised) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
+    }
+#else
+    (void)young;
+    if (raised) __builtin_amdgcn_s_setprio(2);
+    else __builtin_amdgcn_s_setprio(0);
+#endif
+}
+
 template <bool IN_RANGE = false, bool PACK = false, bool YIELD = false, bool PAIR0 = false, int LSTRIDE = 4, bool MAPPED = false>
 __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], const int* __restrict__ tab, float px, float py, float pz, int q,
-                                               float bound, float two_bound, float (&encx)[9]) {
+                                               float bound, float two_bound, float (&encx)[9], bool young = false) {
     // the three grid levels this lane touches (level = 4 m + q); read per slice from LDS so that they do not occupy registers during the
     // matrix phase
     uint32_t lv_off[3], lv_strd[3], lv_hmul[3], lv_mask[3];
@@ -216,13 +252,14 @@ __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], con
             gv[i][c] = *reinterpret_cast<const float*>(gb + (index << 2));
         }
     }
-    if constexpr (YIELD) __builtin_amdgcn_s_setprio(0);
+    if constexpr (YIELD) lz_wave_prio(false, young);
     asm volatile("" ::"v"(gv[0][0]), "v"(gv[0][1]), "v"(gv[0][2]), "v"(gv[0][3]), "v"(gv[1][0]), "v"(gv[1][1]), "v"(gv[1][2]),
                  "v"(gv[1][3]), "v"(gv[2][0]), "v"(gv[2][1]), "v"(gv[2][2]), "v"(gv[2][3]), "v"(gv[3][0]), "v"(gv[3][1]),
                  "v"(gv[3][2]), "v"(gv[3][3]), "v"(gv[4][0]), "v"(gv[4][1]), "v"(gv[4][2]), "v"(gv[4][3]), "v"(gv[8][0]),
                  "v"(gv[8][1]), "v"(gv[8][2]), "v"(gv[8][3]), "v"(gv[7][0]), "v"(gv[7][1]), "v"(gv[7][2]), "v"(gv[7][3]));
     asm volatile("" ::"v"(gv[5][0]), "v"(gv[5][1]), "v"(gv[5][2]), "v"(gv[5][3]), "v"(gv[6][0]), "v"(gv[6][1]), "v"(gv[6][2]),
                  "v"(gv[6][3]));
+    if constexpr (YIELD && LZF_PRIO_TAIL != 0) lz_wave_prio(true, young);      // the loads have returned: interpolate in one burst
     // bilinear weights in the reference's corner order, w = (1 * w0) * w1 with w_d = 1 - f_d or f_d (gridencoder.cu:141-152), fma chain
     if constexpr (PACK) {
         // features (i, i + 1) of a plane share the coordinates and differ in the level: two of them per packed instruction; the ninth
@@ -267,5 +304,6 @@ __device__ __forceinline__ void lz_head_gather(const float* const (&emb)[3], con
             encx[i] = oob ? 0.0f : encx[i];
         }
     }
+    if constexpr (YIELD && LZF_PRIO_TAIL != 0) lz_wave_prio(false, young);     // the matrix phase behind runs at the base priority
 }
 #endif

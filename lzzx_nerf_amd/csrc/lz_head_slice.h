@@ -21,6 +21,7 @@ struct LzHeadCtx {
     float bound, two_bound, eye_v, indq;
     const float* lind;      // LDS: ind_code [4] (0 without one)
     bool has_eye, has_ind;
+    bool young;             // lz_wave_prio (lz_head_gather.h): the fused frame kernel sets it per wave, false elsewhere
 };
 
 struct LzHeadOut {
@@ -58,6 +59,7 @@ __device__ __forceinline__ void lz_head_stage(const LzHeadArgs& P, float* wl, ui
     hc.has_ind = P.ind_code != nullptr;
     if (threadIdx.x < 4) wl[L::TAB + LZ_LVTAB_IND + threadIdx.x] = P.ind_code ? P.ind_code[threadIdx.x] : 0.0f;
     hc.lind = wl + L::TAB + LZ_LVTAB_IND;
+    hc.young = false;
 }
 
 // SH(4) source that evaluates the polynomials from a direction fetched on demand (the stand-alone kernels: dirs are per sample)
@@ -147,6 +149,16 @@ __device__ __forceinline__ void lz_slice_relu_fence() {
 #endif
 }
 
+// The vector instructions that still stood alone between two MFMAs of the wave's own chain (17 in lz_k_frame<0, 1, 1>; tools/isa_census.py
+// --gaps names them) were of two kinds.  Five v_mul_f32 of the sigma net's enc_a * att inputs, which the scheduler sinks to the k-step that
+// consumes each: a fence behind the eight products keeps them ahead of the layer's first MFMA.  Twelve v_max_i32 of sigma_net.0's ReLU:
+// the SH partial's loads (LzShPartial::issue: a load under a per-lane condition, so a branch) stood between the ReLU block's fence and
+// sigma_net.1, a scheduling barrier holds only inside its basic block, and the ReLUs had been sunk into the block behind the branch.  The
+// loads are issued ahead of the ReLU block instead.  LZ_SLICE_GAP_FENCE = 0 restores the former order (A/B switch).
+#ifndef LZ_SLICE_GAP_FENCE
+#define LZ_SLICE_GAP_FENCE 1
+#endif
+
 // one slice: (px, py, pz) = this lane's sample position; shfn supplies SH(4) of its view direction when the colour net needs it
 // (LzShFromDir: evaluated here from the direction, like the reference per sample), or the colour net's SH partial of the sample's ray
 // (LzShPartial: the fused frame kernel, which evaluates k-steps 0 .. 3 of colour_net.0 once per ray)
@@ -161,7 +173,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
     const int q = lane >> 4;
     // ---------------- gather: enc_x features f = 4i + q of sample s -> B operands (lz_head_gather.h) ----------------
     float encx[LZ_T][9];
-    lz_head_gather<IN_RANGE, LZ_GATHER_PACK32, YIELD, true>(hc.emb, hc.tab, px, py, pz, q, hc.bound, hc.two_bound, encx[0]);
+    lz_head_gather<IN_RANGE, LZ_GATHER_PACK32, YIELD, true>(hc.emb, hc.tab, px, py, pz, q, hc.bound, hc.two_bound, encx[0], hc.young);
     __builtin_amdgcn_sched_barrier(0);  // the tile's 36 reads in flight at a time: bounds the register footprint
 
     // ---------------- audio channel attention: 36 -> 64 -> 32 ----------------
@@ -261,6 +273,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
                 for (int r = 0; r < 4; r++) b1[j][9 + 4 * t + r] = hc.lenca[16 * t + 4 * q + r] * att[j][4 * t + r];
             b1[j][17] = 0.0f;           // (k-step 17 runs on the VALU below)
         }
+        if constexpr (LZ_SLICE_GAP_FENCE != 0) lz_slice_relu_fence();
         lz_f4 acc1[4][LZ_T];
 #pragma unroll
         for (int ft = 0; ft < 4; ft++)
@@ -285,6 +298,8 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
                 }
             }
         }
+        // the per-ray SH partial of colour_net.0 (LzShPartial): its loads fly under sigma_net.1 / .2
+        if constexpr (LZ_SLICE_GAP_FENCE != 0) shfn.issue(q);
         float b2[LZ_T][16];
 #pragma unroll
         for (int j = 0; j < LZ_T; j++)
@@ -293,7 +308,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
                 for (int r = 0; r < 4; r++) b2[j][4 * ft + r] = lz_slice_relu(acc1[ft][j][r]);
         lz_slice_relu_fence();
-        shfn.issue(q);            // the per-ray SH partial of colour_net.0 (LzShPartial): its loads fly under sigma_net.1 / .2
+        if constexpr (LZ_SLICE_GAP_FENCE == 0) shfn.issue(q);
         lz_f4 acc2[4][LZ_T];
 #pragma unroll
         for (int ft = 0; ft < 4; ft++)
@@ -363,6 +378,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
         // f32 frame 1.1 % faster; the same move for a per-sample k-step, whose B values first cross lanes, was 3-6 % SLOWER).  Without
         // ind_code the k-step adds zeros only: skipped.  (The folded kernels kept this k-step on the matrix pipe while the VALU form spilled
         // them; built without the SLP vectoriser -- build.py: FILE_FLAGS -- it does not, and they issue 273 MFMAs per slice instead of 277.)
+        if constexpr (YIELD && LZF_PRIO_TAIL != 0) lz_wave_prio(true, hc.young);     // the slice's vector tail, held through the compositing
         if (hc.has_ind) {
             const float* w80 = hc.wl + (lz_frag_base(LZ_L_C1) + 20 * LZ_NT[LZ_L_C1]) * 64 + 4 * q;
             const lz_f4 ind = *reinterpret_cast<const lz_f4*>(hc.lind);      // (one broadcast read)

@@ -5,6 +5,7 @@ Markers move a little with instruction scheduling: read neighbouring sections to
 
     python tools/isa_census.py            # the f16 fused frame kernel lz_k_frame<1, 1, 2>
     python tools/isa_census.py --f32      # the f32 one, lz_k_frame<0, 1, 1> (the headline launch), by the sections of lz_head_slice.h
+    python tools/isa_census.py --gaps [-DLZF_PRIO_TAIL=1 ...]   # both f32 frame kernels: vector instructions between MFMAs, s_setprio
 
 The summary line counts, over the whole kernel, four things the source intends and a compiler can quietly undo: 8-byte table loads (the
 dense levels' paired corners), packed f32 vector ops (the SLP vectoriser's), canonicalising v_max_f32 (both sources the same register:
@@ -75,7 +76,55 @@ def summary_counts(ins):
             "canonicalising_v_max_f32": sum(map(is_canonicalising_max, ins)), "v_lshl_add_u64": sum(t.startswith("v_lshl_add_u64") for t in ins)}
 
 
+def mfma_gaps(ins):
+    """[(number of the MFMA in front, [vector instructions that are no MFMA])] for every interval between two consecutive MFMAs of the kernel
+    that holds any.  Beside f32 MFMAs, opening such a gap costs more than each further instruction in it (tools/probes): the intervals
+    with exactly one instruction are the ones worth closing."""
+    at = [i for i, t in enumerate(ins) if t.startswith("v_mfma")]
+    out = []
+    for n, (a, b) in enumerate(zip(at, at[1:])):
+        v = [t for t in ins[a + 1:b] if t.startswith("v_")]
+        if v:
+            out.append((n, v))
+    return out
+
+
+def single_gaps(ins):
+    return [(n, v[0]) for n, v in mfma_gaps(ins) if len(v) == 1]
+
+
+def setprio(ins):
+    """the kernel's s_setprio instructions in program order, as their priorities"""
+    return [int(t.split()[1]) for t in ins if t.startswith("s_setprio")]
+
+
+def frame_isa(extra_flags=(), out=None):
+    """lz_frame.hip compiled to ISA with the library's own flags (the f32 compilation) and `extra_flags` (-D switches)"""
+    sys.path.insert(0, ROOT)
+    from lzzx_nerf_amd import build as B
+    out = out or os.path.join(TMP + "_isa", "lz_frame.s")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    flags = [f for f in B.FLAGS if not f.startswith("-Rpass")] + B.FILE_FLAGS.get("lz_frame.hip", []) + list(extra_flags)
+    subprocess.run([B._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(B.CSRC, "lz_frame.hip"), "-o", out], check=True, capture_output=True)
+    return open(out).read()
+
+
+def gaps_report(extra_flags):
+    """--gaps [-DSWITCH=V ...]: per f32 frame kernel the intervals between MFMAs that hold vector instructions, the single ones by name"""
+    asm = frame_isa(extra_flags)
+    for kernel in (KERNEL_F32, KERNEL_F32_FOLD):
+        ins = kernel_instructions(asm, kernel)
+        gaps = mfma_gaps(ins)
+        one = single_gaps(ins)
+        print("%s: %d MFMAs, %d intervals with vector instructions, %d with exactly one, s_setprio %s" % (
+            kernel, sum(t.startswith("v_mfma") for t in ins), len(gaps), len(one), setprio(ins)))
+        for n, t in one:
+            print("    behind MFMA %3d: %s" % (n, t))
+
+
 def main():
+    if "--gaps" in sys.argv:
+        return gaps_report([a for a in sys.argv[1:] if a.startswith("-D")])
     pos = [a for a in sys.argv[1:] if not a.startswith("-")]
     f32 = "--f32" in sys.argv
     KERNEL = pos[0] if pos else (KERNEL_F32 if f32 else KERNEL_F16)
