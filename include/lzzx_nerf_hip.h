@@ -424,6 +424,15 @@ int lz_torso_anchor_encode(const float* pose, const float* anchor_points, float*
 /* bg_coords [N,2] in [-1,1] -> alpha [N], color [N,3], deform [N,2] (may be NULL); unmasked pixels get zeros */
 int lz_torso_forward(const lz_torso_params* p, const float* bg_coords, uint32_t N, float* alpha, float* color, float* deform,
                      lz_stream_t stream);
+/* The clip front end of the torso (lzzx_nerf_amd/pipeline.py, TalkingHeadFrame.render_clip).  Additive under ABI version 11.
+ * lz_torso_anchor_encode_batch: poses [K,4,4] -> enc_anchor [K,42], workgroup k = lz_torso_anchor_encode of pose k (same bits), one
+ * launch for the clip; K = 0 returns LZ_OK.
+ * lz_torso_forward_mixed: lz_torso_forward with run_torso's background mix (renderer.py:621) in the store: color_mixed [N,3] =
+ * fl(fl(c a) + fl(b fl(1 - a))) per channel, b = bg [N,3] or, when bg is NULL, bg_scalar; alpha and deform as lz_torso_forward.  A pixel
+ * the occupancy mask drops has a = c = 0 in that formula (it stores b).  N = 0 returns LZ_OK. */
+int lz_torso_anchor_encode_batch(const float* poses, const float* anchor_points, float* enc_anchor, uint32_t K, lz_stream_t stream);
+int lz_torso_forward_mixed(const lz_torso_params* p, const float* bg_coords, uint32_t N, const float* bg, float bg_scalar, float* alpha,
+                           float* color_mixed, float* deform, lz_stream_t stream);
 
 /* ---- Torso training (lzzx_nerf_amd/torso_train.py, FusedTorsoTrainNet; csrc/lz_torso_train.hip) ---------------------------------
  * Additive under ABI version 11.  The forward is lz_torso_forward's arithmetic (same bits for alpha, colour, deform) plus a threshold
@@ -475,6 +484,20 @@ typedef struct {
 /* workspace: n_win * 256 floats (device), used when dim_in >= 128 (the first layer then runs as its own chip-wide launch, one
  * wave per output, with a lane-strided summation order); may be NULL for narrower inputs */
 int lz_audio_encode(const lz_audio_params* p, const float* a, float* enc_a, void* workspace, lz_stream_t stream);
+/* The audio codes of a clip's frames from the whole feature track (csrc/lz_audio.hip; FusedAudioEncoder.encode_track).  Additive under
+ * ABI version 11.  features [T, dim_in, 16] is the track, one row per frame; frame i of [start, start + count) reads row i (att_mode 0),
+ * rows [i - 8, i) (att_mode 1) or [i - 4, i + 4) (att_mode 2), a row outside [0, T) being a window of zeros (nerf_triplane/utils.py:20-52).
+ * Stage A runs AudioNet once per row the frames touch and once on the zero window (workgroups of up to 8 windows); stage B, one small
+ * workgroup per frame, gathers the frame's 8 results and runs AudioAttNet (att_mode 1 / 2; p->n_win is ignored, AudioAttNet's seq_len is
+ * 8); stage C is opt.smooth_lips over the clip, e[k] = fl(fl(w_prev e[k-1]) + fl(w_cur own[k])) with e[-1] = enc_a_prev [dim_aud] -- NULL:
+ * frame `start` keeps its own code -- and runs unless w_prev and w_cur are both 0.  enc_a [count, dim_aud]: every row has the bits of
+ * lz_audio_encode on that frame's windows.  Five launches and a memset for the clip at most, no host synchronisation, no allocation.
+ * count = 0 returns LZ_OK; start + count <= T; att_mode > 2, or 1 / 2 without attention weights: LZ_ERR_UNSUPPORTED.
+ * workspace: lz_audio_track_workspace(count, dim_in, dim_aud) device bytes (a zeroed window, the per-row results, the wide first
+ * layer's outputs when dim_in >= 128); no initialisation needed. */
+size_t lz_audio_track_workspace(uint32_t count, uint32_t dim_in, uint32_t dim_aud);
+int lz_audio_encode_track(const lz_audio_params* p, const float* features, uint32_t T, uint32_t att_mode, uint32_t start, uint32_t count,
+                          float w_prev, float w_cur, const float* enc_a_prev, float* enc_a, void* workspace, lz_stream_t stream);
 
 /* ---- Audio encoder training (lzzx_nerf_amd/audio_train.py, FusedAudioTrainNet; csrc/lz_audio_train.hip) -------------------------
  * Additive under ABI version 11.  The forward is lz_audio_encode itself.  The backward of encode_audio (network.py:226-240) with

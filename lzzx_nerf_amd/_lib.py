@@ -172,11 +172,15 @@ SIGNATURES = {
     "lz_head_pack_weights_f16w": [vp] * 9 + [i32, i32, vp, vp],
     "lz_torso_forward": [C.POINTER(TorsoParams), vp, u32, vp, vp, vp, vp],
     "lz_torso_anchor_encode": [vp, vp, vp, vp],
+    # the clip front end (lzzx_nerf_amd/pipeline.py: TalkingHeadFrame.render_clip)
+    "lz_torso_anchor_encode_batch": [vp, vp, vp, u32, vp],
+    "lz_torso_forward_mixed": [C.POINTER(TorsoParams), vp, u32, vp, f32, vp, vp, vp, vp],
     # torso training (csrc/lz_torso_train.hip, lzzx_nerf_amd/torso_train.py)
     "lz_torso_train_forward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, vp],
     "lz_torso_train_backward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, C.POINTER(TorsoGrads), vp, vp],
     "lz_torso_anchor_encode_backward": [vp, vp, vp, u32, vp, vp],
     "lz_audio_encode": [C.POINTER(AudioParams), vp, vp, vp, vp],
+    "lz_audio_encode_track": [C.POINTER(AudioParams), vp, u32, u32, u32, u32, f32, f32, vp, vp, vp, vp],
     # audio encoder training (csrc/lz_audio_train.hip, lzzx_nerf_amd/audio_train.py)
     "lz_audio_train_backward": [C.POINTER(AudioParams), vp, vp, vp, C.POINTER(AudioGrads), vp, vp],
     "lz_mark_untrained_grid": [vp, u32, f32, f32, f32, f32, u32, u32, f32, vp, vp, vp],
@@ -212,7 +216,7 @@ LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
-         "lz_audio_train_workspace": ([], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
+         "lz_audio_train_workspace": ([], C.c_size_t), "lz_audio_track_workspace": ([u32, u32, u32], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
          "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))

@@ -5,13 +5,17 @@
     bg_coords, head pose --torso--> background   (1 launch,  lzzx_nerf_amd.torso; skipped without torso weights)
     rays --march / head / composite loop--> rgb  (3 + 4 per iteration launches, lzzx_nerf_amd.renderer), blended over that background
 
-All stages read the reference's state_dict; nothing synchronises with the host except the render loop's bounded look-ahead."""
+All stages read the reference's state_dict; nothing synchronises with the host except the render loop's bounded look-ahead.
+
+A clip of frames from one audio track goes through `TalkingHeadFrame.render_clip`: the audio codes of all frames and the anchor
+encodings of all poses once per clip, then per frame the rays, the torso (which writes the mixed background) and the head."""
 import torch
 
 from .audio import FusedAudioEncoder
 from .head import FusedTriplaneHead
 from .renderer import TriplaneRenderer
 from .torso import FusedTorso
+from .utils import frame_rays
 
 
 def audio_window(features, att_mode, index):
@@ -35,8 +39,24 @@ def audio_window(features, att_mode, index):
     return out
 
 
+def audio_track_windows(T, att_mode):
+    """`audio_window` for every frame of a track of T rows at once, as an index table: int64 [T, n_win] (n_win = 1 for att_mode 0, else 8),
+    entry [i, t] = the track row that is window t of frame i, or T for a window of zeros.  Gathering cat(features, zeros)[table[i]]
+    is audio_window(features, att_mode, i); it is the rule lz_audio_encode_track applies on the device."""
+    i = torch.arange(T, dtype=torch.int64)[:, None]
+    if att_mode == 0:
+        return i
+    if att_mode == 1:
+        rows = i - 8 + torch.arange(8, dtype=torch.int64)[None, :]
+    elif att_mode == 2:
+        rows = i - 4 + torch.arange(8, dtype=torch.int64)[None, :]
+    else:
+        raise NotImplementedError(f"wrong att_mode: {att_mode}")
+    return torch.where((rows < 0) | (rows >= T), torch.full_like(rows, T), rows)
+
+
 class TalkingHeadFrame:
-    SMOOTH_LIPS_LAMBDA = 0.35   # renderer.py:254-258, 456-460
+    SMOOTH_LIPS_LAMBDA = FusedAudioEncoder.SMOOTH_LIPS_LAMBDA   # 0.35: renderer.py:254-258, 456-460
 
     def __init__(self, state_dict, density_bitfield, bound=1.0, exp_eye=True, torso_shrink=0.8, precision="f32", device="cuda",
                  smooth_lips=False, fold_geo=False, **renderer_kw):
@@ -103,3 +123,39 @@ class TalkingHeadFrame:
         out = self.renderer.render(rays_o, rays_d, enc_a, ind_code, eye, bg_color=bg_color, **render_kw)
         out.update(extra)
         return out
+
+    @torch.no_grad()
+    def render_clip(self, poses, intrinsics, H, W, features, att_mode, first_index=0, eyes=None, ind_code=None, ind_code_torso=None,
+                    bg_coords=None, bg_color=1.0, density_grid_torso=None, density_thresh_torso=None, **render_kw):
+        """A clip of K = len(poses) frames from one audio track: a generator of one dict per frame, the dict `render` returns for that
+        frame (same keys, same bits; like `render`'s, its tensors are the renderer's buffers and are overwritten by the next frame).
+        poses [K,4,4]; features [T, dim_in, 16], frame k uses audio index first_index + k (`audio_window`) and eyes[k]; full H x W frames.
+
+        What belongs to the clip runs once: the audio codes of all frames from the whole track (FusedAudioEncoder.encode_track, with
+        smooth_lips folded in), the anchor encodings of all poses (FusedTorso.encode_anchors).  Per frame: the rays, the torso with the
+        background mix in its store, the head.  The smooth_lips state continues from and is handed on to `render` / `render_clip`."""
+        poses = torch.as_tensor(poses).to(self.audio.device, torch.float32).reshape(-1, 4, 4).contiguous()
+        K = poses.shape[0]
+        enc = self.audio.encode_track(features, att_mode, first_index, K, self.smooth_lips, self._enc_a_prev)
+        torso = self.torso is not None and bg_coords is not None
+        if torso:
+            if density_grid_torso is None:
+                density_grid_torso = getattr(self, "density_grid_torso", None)
+            if density_thresh_torso is None:
+                density_thresh_torso = getattr(self, "density_thresh_torso", 0.0) if density_grid_torso is not None else 0.0
+            anchors = self.torso.encode_anchors(poses)
+            mix_bg = bg_color.reshape(-1, 3) if torch.is_tensor(bg_color) else float(bg_color)
+        for k in range(K):
+            enc_a = enc[k:k + 1]
+            if self.smooth_lips:
+                self._enc_a_prev = enc_a
+            extra = dict(enc_a=enc_a)
+            bg = bg_color
+            rays_o, rays_d = frame_rays(poses[k], intrinsics, H, W)
+            if torso:
+                alpha, bg, deform = self.torso(bg_coords, None, ind_code_torso, density_grid=density_grid_torso, density_thresh=density_thresh_torso,
+                                               enc_anchor=anchors[k], mix_bg=mix_bg)
+                extra.update(torso_alpha=alpha, torso_color=bg, deform=deform)
+            out = self.renderer.render(rays_o, rays_d, enc_a, ind_code, None if eyes is None else eyes[k], bg_color=bg, **render_kw)
+            out.update(extra)
+            yield out

@@ -42,10 +42,19 @@ class FusedTorso:
         call("lz_torso_anchor_encode", ptr(pose), ptr(self.anchor_points), ptr(enc), stream())   # one launch; torch.inverse alone is a dozen
         return enc
 
+    def encode_anchors(self, poses):
+        """encode_anchor for the K head poses of a clip in one launch: [K,4,4] -> [K, 42], row k = encode_anchor(poses[k]) bit for bit"""
+        poses = poses.to(self.device, torch.float32).reshape(-1, 4, 4).contiguous()
+        K = poses.shape[0]
+        enc = torch.empty(K, 42, dtype=torch.float32, device=self.device)
+        call("lz_torso_anchor_encode_batch", ptr(poses), ptr(self.anchor_points), ptr(enc), K, stream())
+        return enc
+
     @torch.no_grad()
-    def forward(self, bg_coords, poses=None, ind_code=None, density_grid=None, density_thresh=0.0, enc_anchor=None):
+    def forward(self, bg_coords, poses=None, ind_code=None, density_grid=None, density_thresh=0.0, enc_anchor=None, mix_bg=None):
         """bg_coords [N,2] in [-1,1].  Returns torso_alpha [N,1], torso_color [N,3], deform [N,2]; pixels whose 2-D occupancy
-        (bilinear sample of density_grid [G*G]) is <= density_thresh get zeros, as in run_torso."""
+        (bilinear sample of density_grid [G*G]) is <= density_thresh get zeros, as in run_torso.  mix_bg (a scalar or a [N,3] background):
+        the second value is `mix_background(torso_alpha, torso_color, mix_bg)` instead, bit for bit, written by the kernel itself."""
         xy = bg_coords.reshape(-1, 2).to(self.device, torch.float32).contiguous()
         N = xy.shape[0]
         if enc_anchor is None:
@@ -69,7 +78,18 @@ class FusedTorso:
             p.density_grid, p.G, p.density_thresh = None, 0, 0.0
         kw = dict(dtype=torch.float32, device=self.device)
         alpha, color, deform = torch.empty(N, 1, **kw), torch.empty(N, 3, **kw), torch.empty(N, 2, **kw)
-        call("lz_torso_forward", C.byref(p), ptr(xy), N, ptr(alpha), ptr(color), ptr(deform), stream())
+        if mix_bg is None:
+            call("lz_torso_forward", C.byref(p), ptr(xy), N, ptr(alpha), ptr(color), ptr(deform), stream())
+        else:
+            bg, bg_scalar = None, 0.0
+            if torch.is_tensor(mix_bg):
+                bg = mix_bg.to(self.device, torch.float32).reshape(-1, 3)
+                bg = (bg.expand(N, 3) if bg.shape[0] == 1 else bg).contiguous()      # one colour for the frame: what broadcasting does
+                if bg.shape[0] != N:
+                    raise RuntimeError("mix_bg must be a scalar or [%d, 3]" % N)
+            else:
+                bg_scalar = float(mix_bg)
+            call("lz_torso_forward_mixed", C.byref(p), ptr(xy), N, ptr(bg), bg_scalar, ptr(alpha), ptr(color), ptr(deform), stream())
         self._keep = (enc_anchor, ind_code, density_grid)
         return alpha, color, deform
 
