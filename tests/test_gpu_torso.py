@@ -6,24 +6,10 @@ import torch
 
 from oracle import oracle as O
 from oracle.torso import run_torso
+from torso_train_cases import graph, torso_state as _torso_state
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-def _torso_state(ind_dim, seed=0):
-    rng = np.random.default_rng(seed)
-    lin = lambda n, k: rng.uniform(-1, 1, (n, k)).astype(F32) / F32(np.sqrt(k))
-    pls = np.exp2(np.log2(2048 / 16) / 15)
-    offsets = O.grid_offsets(2, 16, pls, 16, 16)
-    K0 = 34 + 42 + ind_dim
-    sd = {"anchor_points": np.array([[0.01, 0.01, 0.1, 1], [-0.1, -0.1, 0.1, 1], [0.1, -0.1, 0.1, 1]], F32),
-          "torso_deform_net.net.0.weight": lin(32, K0), "torso_deform_net.net.1.weight": lin(32, 32),
-          "torso_deform_net.net.2.weight": lin(2, 32) * F32(0.2),
-          "torso_net.net.0.weight": lin(32, 32 + K0), "torso_net.net.1.weight": lin(32, 32), "torso_net.net.2.weight": lin(4, 32),
-          "torso_encoder.embeddings": rng.uniform(-1, 1, (int(offsets[-1]), 2)).astype(F32),
-          "torso_encoder.offsets": offsets.astype(np.int32)}
-    return sd
 
 
 @pytest.mark.parametrize("ind_dim,masked", [(8, True), (0, True), (8, False)])
@@ -195,46 +181,9 @@ def test_torso_trains_through_the_operator_path():
     grads = {k: p.grad.detach().double().cpu() for k, p in net.named_parameters() if p.grad is not None}
     assert {"torso_net.net.0.weight", "torso_deform_net.net.2.weight", "torso_encoder.embeddings", "anchor_points"} <= set(grads)
 
-    # float64 model of the same graph in plain torch (dense bilinear interpolation of the tiled grid written out)
-    P = {k: torch.from_numpy(v).double().requires_grad_(v.dtype == F32) for k, v in sd.items() if k != "torso_encoder.offsets"}
-    offs = sd["torso_encoder.offsets"].astype(np.int64)
-
-    def freq(v, deg):
-        outs = [v]
-        for k in range(deg):
-            outs += [torch.sin(v * 2.0 ** k), torch.cos(v * 2.0 ** k)]
-        return torch.cat(outs, -1)
-
-    def tiled_grid(u01):
-        feats = []
-        S = np.log2(2048 / 16) / 15
-        for l in range(16):
-            scale = float(np.float32(np.exp2(np.float32(l) * np.float32(S)) * np.float32(16) - np.float32(1)))
-            res = int(np.ceil(scale)) + 1
-            size = int(offs[l + 1] - offs[l])
-            pos = u01 * scale + 0.5
-            g0 = torch.floor(pos).detach()
-            fr = pos - g0
-            g0 = g0.long()
-            acc = 0
-            for cx in (0, 1):
-                for cy in (0, 1):
-                    ix, iy = g0[:, 0] + cx, g0[:, 1] + cy
-                    idx = (ix + iy * (res + 1)) % size                     # tiled: wrap the dense index (gridencoder.cu:54-72)
-                    w = (fr[:, 0] if cx else 1 - fr[:, 0]) * (fr[:, 1] if cy else 1 - fr[:, 1])
-                    acc = acc + w[:, None] * P["torso_encoder.embeddings"][offs[l] + idx]
-            feats.append(acc)
-        return torch.cat(feats, -1)
-
-    xd = x.double().cpu() * 0.8
-    wrapped = P["anchor_points"][None] @ torch.from_numpy(pose[None]).double().permute(0, 2, 1).inverse()
-    wrapped = (wrapped[:, :, :2] / wrapped[:, :, 3, None] / wrapped[:, :, 2, None]).view(1, -1)
-    h = torch.cat([freq(xd, 8), freq(wrapped, 3).repeat(N, 1), c.double().cpu().repeat(N, 1)], -1)
-    mlp = lambda v, name: torch.relu(torch.relu(v @ P[f"{name}.net.0.weight"].T) @ P[f"{name}.net.1.weight"].T) @ P[f"{name}.net.2.weight"].T
-    dxd = mlp(h, "torso_deform_net")
-    xx = (xd + dxd).clamp(-1, 1)
-    hh = mlp(torch.cat([tiled_grid((xx + 1) / 2), h], -1), "torso_net")
-    out = torch.sigmoid(hh) * 1.002 - 0.001
+    # float64 model of the same graph in plain torch (tests/torso_train_cases.py: dense bilinear interpolation of the tiled grid written out)
+    m = graph(sd, x, pose[None], c, torch.float64, 0.8)
+    P, out, dxd = m.P, torch.cat([m.alpha, m.color], -1), m.deform
     ref_loss = ((out - target.double().cpu()) ** 2).mean() + 1e-2 * (dxd ** 2).mean()
     ref_loss.backward()
     assert float(loss) == pytest.approx(float(ref_loss), rel=1e-5)

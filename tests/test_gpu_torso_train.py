@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from test_gpu_torso import _torso_state
+from torso_train_cases import model
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -65,57 +66,9 @@ def FusedTorso_mix(a, c, bg):
     return FusedTorso.mix_background(a, c, bg)
 
 
-def _f64_grads(sd, xy, pose, c, g_alpha, g_color, g_dx, mask=None):
-    """float64 torch model of forward_torso (the model of test_gpu_torso.py's operator-path test) -> gradients of
-    sum(alpha g_alpha + color g_color + dx g_dx) over the masked pixels"""
-    P = {k: v.double().clone().requires_grad_(True) for k, v in sd.items() if k != "torso_encoder.offsets"}
-    offs = sd["torso_encoder.offsets"].numpy().astype(np.int64)
-    cd = c.double().cpu().clone().requires_grad_(True) if c is not None else None
-
-    def freq(v, deg):
-        outs = [v]
-        for k in range(deg):
-            outs += [torch.sin(v * 2.0 ** k), torch.cos(v * 2.0 ** k)]
-        return torch.cat(outs, -1)
-
-    def tiled_grid(u01):
-        feats = []
-        S = np.log2(2048 / 16) / 15
-        for l in range(16):
-            scale = float(np.float32(np.exp2(np.float32(l) * np.float32(S)) * np.float32(16) - np.float32(1)))
-            res = int(np.ceil(scale)) + 1
-            size = int(offs[l + 1] - offs[l])
-            pos = u01 * scale + 0.5
-            g0 = torch.floor(pos).detach()
-            fr = pos - g0
-            g0 = g0.long()
-            acc = 0
-            for cx in (0, 1):
-                for cy in (0, 1):
-                    idx = (g0[:, 0] + cx + (g0[:, 1] + cy) * (res + 1)) % size
-                    w = (fr[:, 0] if cx else 1 - fr[:, 0]) * (fr[:, 1] if cy else 1 - fr[:, 1])
-                    acc = acc + w[:, None] * P["torso_encoder.embeddings"][offs[l] + idx]
-            feats.append(acc)
-        return torch.cat(feats, -1)
-
-    xd = xy.double().cpu() * 0.8
-    N = xd.shape[0]
-    wrapped = P["anchor_points"][None] @ pose.double().cpu().permute(0, 2, 1).inverse()
-    wrapped = (wrapped[:, :, :2] / wrapped[:, :, 3, None] / wrapped[:, :, 2, None]).view(1, -1)
-    parts = [freq(xd, 8), freq(wrapped, 3).repeat(N, 1)] + ([cd.repeat(N, 1)] if cd is not None else [])
-    h = torch.cat(parts, -1)
-    mlp = lambda v, name: torch.relu(torch.relu(v @ P[f"{name}.net.0.weight"].T) @ P[f"{name}.net.1.weight"].T) @ P[f"{name}.net.2.weight"].T
-    dxd = mlp(h, "torso_deform_net")
-    xx = (xd + dxd).clamp(-1, 1)
-    out = torch.sigmoid(mlp(torch.cat([tiled_grid((xx + 1) / 2), h], -1), "torso_net")) * 1.002 - 0.001
-    m = torch.ones(N, 1, dtype=torch.float64) if mask is None else mask.double().cpu()[:, None]
-    L = ((out[:, :1] * g_alpha.double().cpu() + (out[:, 1:] * g_color.double().cpu()).sum(-1, keepdim=True) +
-          (dxd * g_dx.double().cpu()).sum(-1, keepdim=True)) * m).sum()
-    L.backward()
-    g = {k: v.grad for k, v in P.items()}
-    if cd is not None:
-        g["ind_code"] = cd.grad
-    return g
+def _f64_grads(sd, xy, pose, c, g_alpha, g_color, g_dx):
+    """float64 torch model of forward_torso (tests/torso_train_cases.py) -> gradients of sum(alpha g_alpha + color g_color + dx g_dx)"""
+    return model(sd, xy, pose, c, g_alpha, g_color, g_dx, torch.float64, 0.8)[0]
 
 
 def _grads(net, xy, poses, c, ga, gc, gd):
