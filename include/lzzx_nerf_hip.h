@@ -465,6 +465,16 @@ int lz_torso_train_forward(const lz_torso_train_params* p, const float* bg_coord
 /* upstream gradients g_alpha [N], g_color [N,3] (of the mixed colour when p->mix), g_deform [N,2]; each may be NULL (zero) */
 int lz_torso_train_backward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha, const float* g_color,
                             const float* g_deform, const lz_torso_grads* grads, void* workspace, lz_stream_t stream);
+/* lz_torso_train_backward without its table scatter (additive under ABI version 11): every other gradient as above, bit for bit;
+ * grads->g_emb is not touched and may be NULL.  Instead the gradient of the grid encoder's output is written for the grid encoder's own
+ * table-gradient entries: denc [16, N, 2] f32, level-major (their grad_layout 0), and u [N, 2] f32, the [0, 1] coordinates the table was
+ * gathered at.  Every pixel's rows are written, so neither needs initialisation; a masked-out or out-of-range pixel gets zeros and
+ * u = -1 in both coordinates, out of range for the grid encoder, whose table-gradient entries skip such a row (u = 0 would pile all of
+ * them onto the corner entries of every level).  lz_grid_encode_backward_ordered / _fixed (denc, u, D 2, C 2, L 16, net.S, net.H, net.gridtype, align_corners 0)
+ * into a zeroed g_emb then give a table gradient that repeats bit for bit; _fixed's is also free of the pixels' order. */
+int lz_torso_train_backward_rows(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha,
+                                 const float* g_color, const float* g_deform, const lz_torso_grads* grads, void* workspace, float* denc,
+                                 float* u, lz_stream_t stream);
 /* the counterpart of lz_torso_anchor_encode: g_enc_anchor [42] -> g_anchor_points [J,4] (written) through the pose inverse and the
  * perspective divide (network.py:179-183).  J must be 3; J = 0 returns LZ_OK. */
 int lz_torso_anchor_encode_backward(const float* pose, const float* anchor_points, const float* g_enc_anchor, uint32_t J,

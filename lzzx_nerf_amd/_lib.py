@@ -178,6 +178,7 @@ SIGNATURES = {
     # torso training (csrc/lz_torso_train.hip, lzzx_nerf_amd/torso_train.py)
     "lz_torso_train_forward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, vp],
     "lz_torso_train_backward": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, C.POINTER(TorsoGrads), vp, vp],
+    "lz_torso_train_backward_rows": [C.POINTER(TorsoTrainParams), vp, u32, vp, vp, vp, C.POINTER(TorsoGrads), vp, vp, vp, vp],
     "lz_torso_anchor_encode_backward": [vp, vp, vp, u32, vp, vp],
     "lz_audio_encode": [C.POINTER(AudioParams), vp, vp, vp, vp],
     "lz_audio_encode_track": [C.POINTER(AudioParams), vp, u32, u32, u32, u32, f32, f32, vp, vp, vp, vp],

@@ -8,7 +8,8 @@
 // Backward: nothing is recorded.  Each wave recomputes the forward of a 16-pixel slice (the chain of lz_torso_net.h) and runs the data
 // gradients back through the layers on the same v_mfma_f32_16x16x4_f32 shape with TRANSPOSED weight fragments (D[k, pixel] =
 // W^T . G): torso net 4 -> 32 -> 32 -> grid features 32 (the enc_x columns need no gradient: x is an input), the grid's dy/dx and
-// the clamp, deform net 2 -> 32 -> 32.  The table gradient is scattered with float atomics.  Weight gradients take pixels as the
+// the clamp, deform net 2 -> 32 -> 32.  The table gradient is scattered with float atomics, or (the ROWS instantiations) the
+// encoder-output gradient is written out for the grid encoder's ordered / order-free table-gradient kernels.  Weight gradients take pixels as the
 // MFMA's k dimension: the slice's layer inputs and output gradients are staged in the wave's LDS as [feature][16 pixels] rows, read
 // back four pixels per lane as one 16-byte load, and accumulated over the wave's slices into 28 16 x 16 tiles (112 registers).
 // Pixel row 34 of the staged frequency features is set to 1, so the tiles' column 34 carries the pixel sums of the first layers'
@@ -123,11 +124,27 @@ __device__ __forceinline__ void lztb_to_b(lzt_f4 (&acc)[2], const float (&relu_o
     }
 }
 
-template <int IND>
+// rows variant: lane (s, q)'s element of pixel n at level q >> 1, channel q & 1; level 2 i + (q >> 1) lies 4 i N floats further on
+__device__ __forceinline__ float* lzt_rows_at(float* __restrict__ denc, uint32_t N, uint32_t n, int q) {
+    return denc + ((size_t)(q >> 1) * N + n) * 2 + (q & 1);
+}
+
+// ROWS = false: the table gradient is scattered into g_emb with float atomics.  ROWS = true: g_emb is not touched; the kernel hands the
+// encoder-output gradient to the grid encoder's table-gradient kernels (lz_grid_encode_backward_ordered / _fixed) instead: denc, level-major
+// [16, N, 2] (their grad_layout 0; lane (s, q) writes element (l N + n) 2 + ch with l = 2 i + (q >> 1), ch = q & 1, so one store
+// instruction fills one 128-byte run per level for the slice's 16 pixels x 2 channels), and u_out [N, 2], the [0, 1] coordinates the
+// table was gathered at.  Every pixel n < N gets its rows, so neither buffer needs initialisation, and a pixel's rows do not depend on
+// its place in a slice.  A pixel that is masked out or out of range, and every pixel of a skipped slice, gets zeros and u = LZT_ROWS_NO_U,
+// a coordinate outside [0, 1]: every table-gradient kernel of the grid encoder drops such a row before it touches the table.  u = 0 would
+// add the same nothing, but all those rows would then meet in the corner entries of every level: measured on the whole frame with 12 % of
+// it masked out, the step took 2.97 instead of 0.97 ms under "fixed" (same-address LDS atomics) and 137 instead of 12.9 ms under
+// "ordered" (one thread walks an entry's segment).
+#define LZT_ROWS_NO_U (-1.0f)
+template <int IND, bool ROWS>
 __global__ void __launch_bounds__(LZT_WG)
 lz_k_torso_train_backward(LzTorsoTrainArgs T, const float* __restrict__ bg_coords, uint32_t N, const float* __restrict__ g_alpha,
                           const float* __restrict__ g_color, const float* __restrict__ g_deform, float* __restrict__ g_emb,
-                          float* __restrict__ partials) {
+                          float* __restrict__ partials, float* __restrict__ denc, float* __restrict__ u_out) {
     constexpr int H = LZ_TORSO_HID, KC = LZ_TORSO_ANCHOR + IND, K1 = LZ_TORSO_GRIDF + LZ_TORSO_FREQ + KC;
     __shared__ float wl[LZT_FRAGS * 64];
     __shared__ __align__(16) float wb[LZTB_FRAGS * 64];
@@ -155,10 +172,24 @@ lz_k_torso_train_backward(LzTorsoTrainArgs T, const float* __restrict__ bg_coord
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = lane & 15, q = lane >> 4;
     float* st = stage + wave * LZTS_WAVE;
+    const uint32_t n_slices = (N + 15) / 16, stride = gridDim.x * (LZT_WG / 64);
+    if constexpr (ROWS) {   // the rows of the slices that the loop below skips, in a loop of their own: a second way round that one, with
+                            // stores in it, makes the compiler keep the 28 accumulator tiles twice
+        for (uint32_t slice = blockIdx.x * (LZT_WG / 64) + wave; slice < n_slices; slice += stride) {
+            const uint32_t n = slice * 16 + s;
+            const bool valid = n < N;
+            const size_t nc = valid ? n : N - 1;
+            const bool live = lzt_masked(T, bg_coords[nc * 2], bg_coords[nc * 2 + 1]) && valid;
+            if (__ballot(live) || !valid) continue;
+            float* drow = lzt_rows_at(denc, N, n, q);
+#pragma unroll
+            for (int i = 0; i < 8; i++) drow[(size_t)i * 4 * N] = 0.0f;
+            if (q < 2) u_out[(size_t)n * 2 + q] = LZT_ROWS_NO_U;
+        }
+    }
     lzt_f4 gw[LZTG_TILES];
 #pragma unroll
     for (int t = 0; t < LZTG_TILES; t++) gw[t] = lzt_f4{0, 0, 0, 0};
-    const uint32_t n_slices = (N + 15) / 16, stride = gridDim.x * (LZT_WG / 64);
     for (uint32_t slice = blockIdx.x * (LZT_WG / 64) + wave; slice < n_slices; slice += stride) {
         const uint32_t n_raw = slice * 16 + s;
         const bool valid = n_raw < N;
@@ -209,6 +240,11 @@ lz_k_torso_train_backward(LzTorsoTrainArgs T, const float* __restrict__ bg_coord
         {
             const bool oob = f.u[0] < 0 || f.u[0] > 1 || f.u[1] < 0 || f.u[1] > 1;
             const int ch = q & 1;
+            float* drow = nullptr;
+            if constexpr (ROWS) {   // lanes q = 0, 1 of a pixel write its two coordinates: 128 contiguous bytes per slice
+                drow = lzt_rows_at(denc, N, n, q);
+                if (valid && q < 2) u_out[(size_t)n * 2 + q] = (live && !oob) ? (q == 0 ? f.u[0] : f.u[1]) : LZT_ROWS_NO_U;
+            }
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int l = 2 * i + (q >> 1);
@@ -216,14 +252,21 @@ lz_k_torso_train_backward(LzTorsoTrainArgs T, const float* __restrict__ bg_coord
                 const float sc = T.a.scale[l];
                 const LztCell cl = lzt_cell(f.u, sc);
                 const float* g = P.emb + (size_t)off0 * 2 + ch;
-                float* gd = g_emb + (size_t)off0 * 2 + ch;
                 float e[4];
+                if constexpr (ROWS) {   // the terms w gg are formed by the table-gradient kernel, from the same cell and weights
+                    if (valid) *drow = (live && !oob) ? gg[i] : 0.0f;
+                    drow += (size_t)4 * N;
 #pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    const uint32_t index = lz_torso_grid_index(P.gridtype, hs, T.a.res[l], cl.g0 + (c & 1), cl.g1 + (c >> 1));
-                    e[c] = g[index];
-                    const float w = ((c & 1) ? cl.f0 : 1 - cl.f0) * ((c >> 1) ? cl.f1 : 1 - cl.f1);
-                    if (live && !oob && gg[i] != 0.0f) unsafeAtomicAdd(gd + index, w * gg[i]);
+                    for (int c = 0; c < 4; c++) e[c] = g[lz_torso_grid_index(P.gridtype, hs, T.a.res[l], cl.g0 + (c & 1), cl.g1 + (c >> 1))];
+                } else {
+                    float* gd = g_emb + (size_t)off0 * 2 + ch;
+#pragma unroll
+                    for (int c = 0; c < 4; c++) {
+                        const uint32_t index = lz_torso_grid_index(P.gridtype, hs, T.a.res[l], cl.g0 + (c & 1), cl.g1 + (c >> 1));
+                        e[c] = g[index];
+                        const float w = ((c & 1) ? cl.f0 : 1 - cl.f0) * ((c >> 1) ? cl.f1 : 1 - cl.f1);
+                        if (live && !oob && gg[i] != 0.0f) unsafeAtomicAdd(gd + index, w * gg[i]);
+                    }
                 }
                 if (live && !oob) {
                     du[0] += gg[i] * sc * ((1 - cl.f1) * (e[1] - e[0]) + cl.f1 * (e[3] - e[2]));
@@ -457,16 +500,25 @@ extern "C" int lz_torso_train_forward(const lz_torso_train_params* p, const floa
     return LZ_OK;
 }
 
-extern "C" int lz_torso_train_backward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha,
-                                       const float* g_color, const float* g_deform, const lz_torso_grads* grads, void* workspace,
-                                       lz_stream_t stream) {
-    if (N == 0) return LZ_OK;
-    LZ_REQUIRE(bg_coords && grads && workspace, LZ_ERR_BAD_ARGUMENT, "torso_train_backward: null tensor");
-    const int rc = lzt_check(p, "torso_train_backward");
+// both backward entries: denc / u non-null selects the rows-emitting kernel, which leaves grads->g_emb alone
+template <int IND, bool ROWS>
+static void lzt_launch_backward(const LzTorsoTrainArgs& t, const lz_torso_params& net, uint32_t nwg, const float* bg_coords, uint32_t N,
+                                const float* g_alpha, const float* g_color, const float* g_deform, float* g_emb, float* part, float* denc,
+                                float* u, const LzTorsoGradOut& G, hipStream_t st) {
+    hipLaunchKernelGGL((lz_k_torso_train_backward<IND, ROWS>), dim3(nwg), dim3(LZT_WG), 0, st, t, bg_coords, N, g_alpha, g_color, g_deform, g_emb,
+                       part, denc, u);
+    hipLaunchKernelGGL((lz_k_torso_train_combine<IND>), dim3(LZTC_BLOCKS + 1), dim3(256), 0, st, part, nwg, net, G);
+}
+
+static int lzt_backward(const char* what, const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha,
+                        const float* g_color, const float* g_deform, const lz_torso_grads* grads, void* workspace, float* denc, float* u,
+                        bool rows, lz_stream_t stream) {
+    LZ_REQUIRE(bg_coords && grads && workspace && (!rows || (denc && u)), LZ_ERR_BAD_ARGUMENT, "%s: null tensor", what);
+    const int rc = lzt_check(p, what);
     if (rc != LZ_OK) return rc;
     LZ_REQUIRE(grads->g_deform_w0 && grads->g_deform_w1 && grads->g_deform_w2 && grads->g_torso_w0 && grads->g_torso_w1 && grads->g_torso_w2 &&
-                   grads->g_emb && grads->g_enc_anchor && (p->net.ind_dim == 0 || grads->g_ind_code),
-               LZ_ERR_BAD_ARGUMENT, "torso_train_backward: incomplete lz_torso_grads");
+                   (rows || grads->g_emb) && grads->g_enc_anchor && (p->net.ind_dim == 0 || grads->g_ind_code),
+               LZ_ERR_BAD_ARGUMENT, "%s: incomplete lz_torso_grads", what);
     const LzTorsoTrainArgs t = lzt_train_args(p);
     // one workgroup per CU (the staging rows and the 28 accumulator tiles fill the LDS and half the register file), at least four
     // slices per wave before the grid is full
@@ -475,17 +527,30 @@ extern "C" int lz_torso_train_backward(const lz_torso_train_params* p, const flo
     LzTorsoGradOut G{grads->g_deform_w0, grads->g_deform_w1, grads->g_deform_w2, grads->g_torso_w0, grads->g_torso_w1, grads->g_torso_w2,
                      grads->g_enc_anchor, grads->g_ind_code};
     hipStream_t st = lz_st(stream);
-    if (p->net.ind_dim == 8) {
-        hipLaunchKernelGGL((lz_k_torso_train_backward<8>), dim3(nwg), dim3(LZT_WG), 0, st, t, bg_coords, N, g_alpha, g_color, g_deform, grads->g_emb, part);
-        LZ_CHECK_LAUNCH("torso_train_backward");
-        hipLaunchKernelGGL((lz_k_torso_train_combine<8>), dim3(LZTC_BLOCKS + 1), dim3(256), 0, st, part, nwg, p->net, G);
+    const bool ind = p->net.ind_dim == 8;
+    if (rows) {
+        if (ind) lzt_launch_backward<8, true>(t, p->net, nwg, bg_coords, N, g_alpha, g_color, g_deform, nullptr, part, denc, u, G, st);
+        else lzt_launch_backward<0, true>(t, p->net, nwg, bg_coords, N, g_alpha, g_color, g_deform, nullptr, part, denc, u, G, st);
     } else {
-        hipLaunchKernelGGL((lz_k_torso_train_backward<0>), dim3(nwg), dim3(LZT_WG), 0, st, t, bg_coords, N, g_alpha, g_color, g_deform, grads->g_emb, part);
-        LZ_CHECK_LAUNCH("torso_train_backward");
-        hipLaunchKernelGGL((lz_k_torso_train_combine<0>), dim3(LZTC_BLOCKS + 1), dim3(256), 0, st, part, nwg, p->net, G);
+        if (ind) lzt_launch_backward<8, false>(t, p->net, nwg, bg_coords, N, g_alpha, g_color, g_deform, grads->g_emb, part, nullptr, nullptr, G, st);
+        else lzt_launch_backward<0, false>(t, p->net, nwg, bg_coords, N, g_alpha, g_color, g_deform, grads->g_emb, part, nullptr, nullptr, G, st);
     }
-    LZ_CHECK_LAUNCH("torso_train_combine");
+    LZ_CHECK_LAUNCH(what);
     return LZ_OK;
+}
+
+extern "C" int lz_torso_train_backward(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha,
+                                       const float* g_color, const float* g_deform, const lz_torso_grads* grads, void* workspace,
+                                       lz_stream_t stream) {
+    if (N == 0) return LZ_OK;
+    return lzt_backward("torso_train_backward", p, bg_coords, N, g_alpha, g_color, g_deform, grads, workspace, nullptr, nullptr, false, stream);
+}
+
+extern "C" int lz_torso_train_backward_rows(const lz_torso_train_params* p, const float* bg_coords, uint32_t N, const float* g_alpha,
+                                            const float* g_color, const float* g_deform, const lz_torso_grads* grads, void* workspace,
+                                            float* denc, float* u, lz_stream_t stream) {
+    if (N == 0) return LZ_OK;
+    return lzt_backward("torso_train_backward_rows", p, bg_coords, N, g_alpha, g_color, g_deform, grads, workspace, denc, u, true, stream);
 }
 
 extern "C" int lz_torso_anchor_encode_backward(const float* pose, const float* anchor_points, const float* g_enc_anchor, uint32_t J,

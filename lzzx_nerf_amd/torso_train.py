@@ -15,10 +15,12 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, gridencoder
 from ._util import as_f32, call, ptr, stream, workspace
 from .encoding import get_encoder
 from .linear import MLP
+
+_TABLE_GRADS = gridencoder._TABLE_GRADS
 
 
 class TorsoTrainNet(nn.Module):
@@ -107,8 +109,23 @@ class _TorsoTrain(Function):
             g.g_deform_w0, g.g_deform_w1, g.g_deform_w2, g.g_torso_w0, g.g_torso_w1, g.g_torso_w2 = [w.data_ptr() for w in ws]
             g.g_emb, g.g_enc_anchor, g.g_ind_code = g_emb.data_ptr(), g_enc.data_ptr(), g_ind.data_ptr() if g_ind is not None else None
             g_alpha, g_color, g_deform = as_f32(g_alpha), as_f32(g_color), as_f32(g_deform)
-            call("lz_torso_train_backward", C.byref(p), ptr(xy), N, ptr(g_alpha), ptr(g_color), ptr(g_deform), C.byref(g),
-                 ptr(_workspace(xy.device)), stream())
+            mode = net.table_grad
+            if mode == "atomic":
+                call("lz_torso_train_backward", C.byref(p), ptr(xy), N, ptr(g_alpha), ptr(g_color), ptr(g_deform), C.byref(g),
+                     ptr(_workspace(xy.device)), stream())
+            else:
+                # the kernel writes d loss / d (grid features), level-major [16, N, 2], and the [0, 1] coordinates it gathered at (every row;
+                # zeros and u = -1, which the grid kernels skip, for masked-out pixels); the grid encoder's table-gradient kernels sum
+                # them into the zeroed g_emb
+                if mode not in _TABLE_GRADS:
+                    raise ValueError("FusedTorsoTrainNet: table_grad must be one of %s, got %r" % (_TABLE_GRADS, mode))
+                denc, u = torch.empty(16, N, 2, dtype=torch.float32, device=xy.device), torch.empty(N, 2, dtype=torch.float32, device=xy.device)
+                call("lz_torso_train_backward_rows", C.byref(p), ptr(xy), N, ptr(g_alpha), ptr(g_color), ptr(g_deform), C.byref(g),
+                     ptr(_workspace(xy.device)), ptr(denc), ptr(u), stream())
+                table_backward = gridencoder.grid_backward_ordered if mode == "ordered" else gridencoder.grid_backward_fixed
+                table_backward(denc, u, emb, meta["offsets"], g_emb, N, 2, 2, 16, net._S, net._H, None, None, 1, False, 0)
+                if net.keep_denc:
+                    net.last_denc, net.last_u = denc, u
         return (None, None, g_enc, g_ind) + tuple(ws) + (g_emb,)
 
 
@@ -119,18 +136,32 @@ class FusedTorsoTrainNet(TorsoTrainNet):
     `torso_encoder.embeddings` / `.offsets`, `torso_net.net.i.weight`), the same initialisation, so a state dict moves between them and
     `torso.FusedTorso`.  Every call reads the live parameter tensors (no packed copies: writes through `.data`, as the reference's EMA
     does, are seen).  The forward gives `FusedTorso`'s bits for alpha, colour and deform.  The backward recomputes the forward and returns
-    every gradient: weights, table (float atomics: repeatable only up to summation order), `anchor_points` (through the pose inverse) and
-    the individual code; MLP weight and frame-constant gradients are reduced in a fixed order (same bits on every call).
+    every gradient: weights, table, `anchor_points` (through the pose inverse) and the individual code; MLP weight and frame-constant
+    gradients are reduced in a fixed order (same bits on every call).
+
+    table_grad: how the table gradient is summed -- a plain attribute, read at every backward.  "atomic" (the default): float atomics
+    inside the backward kernel, repeatable only up to summation order.  "ordered" / "fixed": the backward kernel writes the gradient of
+    the grid features instead ([16, N, 2], with the [0, 1] coordinates it gathered at) and `gridencoder.grid_backward_ordered` /
+    `grid_backward_fixed` sum it into the table: the same bits on every call, and with "fixed" under any order of the pixels as well
+    (every term quantised with one power-of-two scale per level and summed as 64-bit integers, so the gradient still scales exactly
+    with a GradScaler's power of two).  Every other gradient has the same bits in all three.  The default does NOT follow
+    `gridencoder.set_table_grad`: a global mode set for another module leaves this one as it was.  With `keep_denc` set, the last
+    "ordered" / "fixed" backward leaves those two tensors in `last_denc` and `last_u` (diagnostics; a masked-out pixel's rows are zeros
+    and its `last_u` is (-1, -1), out of range for the grid encoder).
 
     Precision: f32 always.  Under `autocast` the inputs are cast to f32 and the kernels run in f32, as `FusedTorso` does (the reference's
     `-O` half-precision Linears are not reproduced).  Works under `GradScaler`: every gradient is linear in the upstream one.
     No host synchronisation: the occupancy threshold may stay a device scalar."""
 
-    def __init__(self, ind_dim_torso=8, torso_shrink=0.8):
+    def __init__(self, ind_dim_torso=8, torso_shrink=0.8, table_grad="atomic"):
         if ind_dim_torso not in (0, 8):
             raise ValueError("FusedTorsoTrainNet: ind_dim_torso must be 0 or 8 (the reference's default)")
+        if table_grad not in _TABLE_GRADS:
+            raise ValueError("FusedTorsoTrainNet: table_grad must be one of %s, got %r" % (_TABLE_GRADS, table_grad))
         super().__init__(ind_dim_torso=ind_dim_torso, torso_shrink=torso_shrink)
         self.ind_dim = ind_dim_torso
+        self.table_grad = table_grad
+        self.keep_denc, self.last_denc, self.last_u = False, None, None
         # GridEncoder hyper-parameters of the torso encoder (network.py:166, grid.py:95-96), as torso.FusedTorso states them
         self._S = float(np.float32(np.log2(np.exp2(np.log2(2048 / 16) / 15))))
         self._H = 16

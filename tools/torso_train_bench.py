@@ -1,7 +1,8 @@
 """Torso stage (train.py --torso): the fused training kernels (lzzx_nerf_amd.torso_train.FusedTorsoTrainNet) against the operator path
 (TorsoTrainNet, an autograd graph over this repo's operators), reference torso configuration, ind_dim_torso 8.
 
-    python tools/torso_train_bench.py [--steps K] [--rounds R] [--sizes 65536,262144] [--only step] [--out profiles/torso_train_bench.json]
+    python tools/torso_train_bench.py [--steps K] [--rounds R] [--sizes 65536,262144] [--only step] [--table-grad fixed]
+                                      [--out profiles/torso_train_bench.json]
 
 At each N (65 536 = train.py's rays per step; 262 144 = the whole 512 x 512 frame):
   (a) TorsoTrainNet forward + backward        (b) FusedTorsoTrainNet forward + backward
@@ -9,7 +10,10 @@ At each N (65 536 = train.py's rays per step; 262 144 = the whole 512 x 512 fram
       reference's boolean-mask gather / scatter composed around TorsoTrainNet, renderer.py:572-631) -> TorsoObjective -> backward ->
       torch.optim.AdamW(betas=(0.0, 0.99), eps=1e-8).
 Variants alternate within each round; each number is the median over rounds of per-round medians of device-event times per call.
-`--only step` runs (c) alone, `--only step_fused` / `--only step_ops` one way of it (the rocprofv3 --kernel-trace --stats runs)."""
+`--only step` runs (c) alone, `--only step_fused` / `--only step_ops` one way of it (the rocprofv3 --kernel-trace --stats runs).
+`--table-grad ordered|fixed` adds, to the same alternation (so the float-atomic fused path of the same run is the yardstick), the fused
+net with that table_grad (`..._fused_..._<mode>`) and the operator path under gridencoder.set_table_grad(<mode>) (`..._ops_..._<mode>`);
+with `--out` the numbers are merged into the file's results under `table_grad_<mode>`, the file's other entries staying as they are."""
 import argparse
 import json
 import os
@@ -22,6 +26,7 @@ import torch.nn.functional as Fn
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from lzzx_nerf_amd import gridencoder  # noqa: E402
 from lzzx_nerf_amd.objective import TorsoObjective  # noqa: E402
 from lzzx_nerf_amd.torso_train import FusedTorsoTrainNet, TorsoTrainNet  # noqa: E402
 
@@ -81,7 +86,7 @@ def run_torso_ops(net, s):
     return color * alpha + 1 * (1 - alpha)
 
 
-def make(s):
+def make(s, table_grad="atomic"):
     fused, ops = s["fused"], s["ops"]
     ga, gc, gd = s["gout"]
     obj = TorsoObjective()
@@ -108,7 +113,27 @@ def make(s):
         loss.backward()
         opt_o.step()
 
-    return {"a_ops_fwd_bwd": fwd_bwd(ops), "b_fused_fwd_bwd": fwd_bwd(fused)}, {"c_step_ops": step_ops, "c_step_fused": step_fused}
+    pairs, steps = {"a_ops_fwd_bwd": fwd_bwd(ops), "b_fused_fwd_bwd": fwd_bwd(fused)}, {"c_step_ops": step_ops, "c_step_fused": step_fused}
+    if table_grad != "atomic":
+        # the same fused net with the attribute switched for the call (it is read at every backward); the operator path under the module
+        # default of the same name.  Both restore "atomic", so the variants they alternate with are the parent's.
+        def in_mode(fn, on_fused):
+            def f():
+                if on_fused:
+                    fused.table_grad = table_grad
+                else:
+                    gridencoder.set_table_grad(table_grad)
+                try:
+                    fn()
+                finally:
+                    fused.table_grad = "atomic"
+                    gridencoder.set_table_grad("atomic")
+            return f
+
+        pairs.update({"a_ops_fwd_bwd_" + table_grad: in_mode(pairs["a_ops_fwd_bwd"], False),
+                      "b_fused_fwd_bwd_" + table_grad: in_mode(pairs["b_fused_fwd_bwd"], True)})
+        steps.update({"c_step_ops_" + table_grad: in_mode(step_ops, False), "c_step_fused_" + table_grad: in_mode(step_fused, True)})
+    return pairs, steps
 
 
 def main():
@@ -117,6 +142,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--sizes", default="65536,262144")
     ap.add_argument("--only", default="")
+    ap.add_argument("--table-grad", default="atomic", choices=["atomic", "ordered", "fixed"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     out = {"device": torch.cuda.get_device_name(0), "steps": a.steps, "rounds": a.rounds, "ind_dim_torso": 8, "results": {}}
@@ -124,19 +150,27 @@ def main():
         s = setup(N)
         with torch.no_grad():
             frac = float((Fn.grid_sample(s["grid"].view(1, 1, 128, 128), s["xy"].view(1, -1, 1, 2), align_corners=True).view(-1) > 0.01).float().mean())
-        pairs, steps = make(s)
+        pairs, steps = make(s, a.table_grad)
         r = {"masked_fraction": frac}
         if not a.only.startswith("step"):
             r.update(alternate(pairs, a.steps, a.rounds))
         if a.only in ("step_fused", "step_ops"):
-            steps = {"c_" + a.only: steps["c_" + a.only]}
+            name = "c_" + a.only + ("_" + a.table_grad if a.table_grad != "atomic" else "")
+            steps = {name: steps[name]}
         r.update(alternate(steps, a.steps, a.rounds))
         out["results"][str(N)] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}
         print(N, out["results"][str(N)], flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        doc = out
+        if a.table_grad != "atomic" and os.path.exists(a.out):   # merged into the float-atomic run's file
+            with open(a.out) as f:
+                doc = json.load(f)
+            doc["table_grad_" + a.table_grad] = {k: out[k] for k in ("device", "steps", "rounds", "results")}
+        elif a.table_grad != "atomic":
+            doc = {"table_grad_" + a.table_grad: out}
         with open(a.out, "w") as f:
-            json.dump(out, f, indent=1)
+            json.dump(doc, f, indent=1)
     print(json.dumps(out))
 
 
