@@ -979,6 +979,14 @@ typedef struct {
 } lz_frame_ngp_fused;
 /* `timing` (may be NULL): one event pair around the phase-1 persistent launch, as lz_frame_render */
 int lz_ngp_frame_render(const lz_frame_ngp_fused* f, struct lz_timing* timing, lz_stream_t stream);
+/* The same frame with `steps_per_pass` = S samples per ray and pass in the persistent kernel (csrc/lz_ngp_frame_spp.hip: a slice's
+ * columns hold 16 / S or 32 / S rays with S consecutive samples each, so a ray needs 1 / S of the dependent passes -- for tiles, crops
+ * and previews, whose rays do not fill the chip's slots).  S is a launch shape only: a ray stops exactly at the cap under either
+ * cap_mode, and every output, the per-ray counts and state [1] [3] [5] [6] [9] [10] [11] are lz_ngp_frame_render's bit for bit at
+ * every S; state [72] counts the slices actually run and differs.  steps_per_pass: 1 = lz_ngp_frame_render's kernels; 2, 4, 8, 16;
+ * 0 = chosen from N, the head's slot width and the CU count (1 whenever the rays fill the slots).  state [13]: the S of an S > 1
+ * launch (0 after the S = 1 kernels).  Anything else: LZ_ERR_BAD_ARGUMENT before any launch.  Additive under ABI version 11. */
+int lz_ngp_frame_render_spp(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, struct lz_timing* timing, lz_stream_t stream);
 /* ---- Hash-grid NeRF training (lzzx_nerf_amd/ngp_train.py, FusedHashgridTrainNeRF; csrc/lz_ngp_train.hip) ----------------------
  * Additive under ABI version 11: new entries only.  Replaces the backward of sigma_net / color_net under autograd (network.py:73-94:
  * Linear, ReLU, cat with the SH features, exp, sigmoid).  The forward is lz_ngp_head_forward on tiled f32 features (feat_layout 1).

@@ -154,6 +154,7 @@ SIGNATURES = {
     "lz_ngp_head_forward_f16": [vp, vp, i32, vp, u32, vp, vp, vp, vp],
     "lz_ngp_loop_run_f16": [C.POINTER(FrameNgp), vp, u32, u32, vp],
     "lz_ngp_frame_render": [C.POINTER(FrameNgpFused), vp, vp],
+    "lz_ngp_frame_render_spp": [C.POINTER(FrameNgpFused), u32, vp, vp],
     # hash-grid NeRF training (csrc/lz_ngp_train.hip, lzzx_nerf_amd/ngp_train.py)
     "lz_ngp_head_backward": [vp] * 7 + [u32] + [vp] * 10,
     "lz_timing_create": [u32, C.POINTER(vp)],

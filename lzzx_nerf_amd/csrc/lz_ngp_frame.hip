@@ -25,36 +25,13 @@
 //     the HBM roofline against 69 % level-major (lz_ngp.hip); inside the frame kernel -- three waves per SIMD, 32 corner loads in flight
 //     per lane, other waves' march / matrix chain / compositing under the misses -- that did not carry over.  Measured:
 //     fused beats the loop everywhere (256^2 x 128 steps f32 1.07 against 3.14 / 1.98 ms, 0.67 of the byte roofline) except on a 64^2
-//     tile with the f16 head under the schedule (8, 8) (0.59 against 0.48 ms).
+//     tile with the f16 head under the schedule (8, 8) (0.59 against 0.48 ms) -- a ray's ~75 dependent passes set a tile's time: for
+//     tiles lz_ngp_frame_spp.hip runs S samples per ray and pass (lz_ngp_frame_render_spp; 0.18 ms in that cell).
 #include <string.h>
 
 #include <mutex>
 
-#include "lz_frame_common.h"
-#include "lz_grid_interp.h"
-#include "lz_ngp_chain.h"
-#include "lz_ngp16_chain.h"
-
-#define LZNF_WG 256
-#define LZNF_WAVES (LZNF_WG / 64)
-#define LZNF_MARCH_PROBES 2      // empty cells a slot may cross per march attempt (as lz_k_frame: the other slots of the wave do not wait for a crossing)
-#define LZNF_LEVELS 16
-
-struct LzNgpFrameArgs {
-    const void* packed;          // PREC 0: LZ_NGP_FRAGS * 64 floats; 1: LZ_NGP_PACKED_F16_BYTES of half fragments
-    const void* emb;             // hash table, f32 or half [offsets[16], 2]
-    const int* offsets;          // [17]
-    LzGridLevels lv;
-    float inv2b;                 // 1.0f / (2 bound): lz_map01's factor
-};
-
-// slot state in LDS, per wave [field][NS]
-enum { NF_RAY = 0, NF_T, NF_FAR, NF_DT, NF_WS, NF_D, NF_R, NF_G, NF_B, NF_CNT,
-       NF_RD,                    // 1 / direction (3), origin (3), direction (3): LzMarch::init reads LDS
-       NF_SH = NF_RD + 9 };      // SH(4) of the direction: 16 floats (f32 head) or 8 words of packed halves (f16 head); behind it the
-                                 // f16 head's parked outputs (rgb[0], rgb[1], rgb[2], sigma: they come out on two lane halves)
-// level records in LDS, [field][16]
-enum { NL_OFF0 = 0, NL_HS, NL_RES, NL_SCALE, NL_MODE, NL_FIELDS };
+#include "lz_ngp_frame_common.h"     // the argument record, the slot fields and what the S > 1 kernels (lz_ngp_frame_spp.hip) share
 
 // PREC: 0 = f32 head (v_mfma_f32_16x16x4_f32), 1 = f16 head (v_mfma_f32_32x32x16_f16); TT: the table's element type
 template <int PREC, typename TT>
@@ -345,7 +322,8 @@ static void lznf_launch(int variant, uint32_t N, const LzNgpFrameArgs& a, const 
     else hipLaunchKernelGGL((lz_k_ngp_frame<0, __half>), dim3(grid), dim3(LZNF_WG), 0, st, a, K);
 }
 
-extern "C" int lz_ngp_frame_render(const lz_frame_ngp_fused* f, lz_timing* timing, lz_stream_t stream) {
+// the frame at `steps_per_pass` samples per ray and pass: 1 = lz_k_ngp_frame, 2 .. 16 = lz_k_ngp_frame_spp, 0 = lznf_spp_auto's choice
+static int lznf_render(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_timing* timing, lz_stream_t stream) {
     LZ_REQUIRE(f, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: null");
     LZ_REQUIRE(f->precision == 0 || f->precision == 1, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: precision must be 0 (f32 head) or 1 (f16 head)");
     LZ_REQUIRE(f->cap_mode == LZ_FRAME_CAP_PER_RAY || f->cap_mode == LZ_FRAME_CAP_REFERENCE, LZ_ERR_BAD_ARGUMENT,
@@ -392,17 +370,31 @@ extern "C" int lz_ngp_frame_render(const lz_frame_ngp_fused* f, lz_timing* timin
     K.ray_last = f->ray_last; K.cap_ws = f->cap_ws; K.cap_mode = f->cap_mode; K.phase2 = 0; K.N_total = f->N_total;
     K.mf = lz_march_frame(f->bound, f->max_steps, f->C, f->H);
     const int variant = f->precision == 1 ? 1 : (f->emb_f16 ? 2 : 0);
+    const uint32_t S = steps_per_pass ? steps_per_pass : lznf_spp_auto(variant, f->N, f->max_steps);
     int rc = lzf_enqueue_queue(K, st);                               // memset + prepare + scatter (lz_frame.hip)
     if (rc != LZ_OK) return rc;
     if (timing) (void)lz_timing_mark(timing, 0, stream);             // the event pair brackets the phase-1 persistent kernel alone
-    lznf_launch(variant, f->N, a, K, st);
+    if (S == 1) lznf_launch(variant, f->N, a, K, st);
+    else lznf_spp_launch(variant, S, f->N, a, K, st);
     if (timing) (void)lz_timing_mark(timing, 1, stream);
     if (f->cap_mode == LZ_FRAME_CAP_REFERENCE) {
         lzf_enqueue_cap_hist(K, true, st);                           // histogram of ray_last, parked rays queued, schedule replay: C_eff
         K.phase2 = 1;
-        lznf_launch(variant, f->N, a, K, st);                        // the parked rays up to C_eff (an early-out launch when none)
+        // the parked rays up to C_eff (an early-out launch when none), in phase 1's launch shape: N bounds their number
+        if (S == 1) lznf_launch(variant, f->N, a, K, st);
+        else lznf_spp_launch(variant, S, f->N, a, K, st);
         if (f->ray_counts) lzf_enqueue_counts(K, st);
     }
     LZ_CHECK_LAUNCH("ngp_frame_render");
     return LZ_OK;
+}
+
+extern "C" int lz_ngp_frame_render(const lz_frame_ngp_fused* f, lz_timing* timing, lz_stream_t stream) {
+    return lznf_render(f, 1, timing, stream);
+}
+
+extern "C" int lz_ngp_frame_render_spp(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_timing* timing, lz_stream_t stream) {
+    LZ_REQUIRE(steps_per_pass == 0 || steps_per_pass == 1 || steps_per_pass == 2 || steps_per_pass == 4 || steps_per_pass == 8 || steps_per_pass == 16,
+               LZ_ERR_BAD_ARGUMENT, "ngp_frame_render_spp: steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %u", steps_per_pass);
+    return lznf_render(f, steps_per_pass, timing, stream);
 }

@@ -205,13 +205,28 @@ class HashgridRenderer:
       Measured on MI355X (loop and fused alternated on one box): fused is faster than the loop in every case measured
       but one -- the 256^2 x 128-step frame 1.07 against 3.14 ms under (1, 8) and 1.98 under (8, 8) (f16 head 0.73 against 2.54 / 1.75;
       half tables + f32 head: see DESIGN), max_steps 16 0.30 against 0.62 ms, a 64^2 tile 0.50 against 2.03 / 0.54 -- and slower only on
-      a 64^2 tile with the f16 head under the fat schedule (8, 8): 0.59 against 0.48 ms.  The default stays "loop"."""
+      a 64^2 tile with the f16 head under the fat schedule (8, 8): 0.59 against 0.48 ms.  The default stays "loop".
+        steps_per_pass (fused only; default 1): samples per ray and pass of the persistent kernel, S = 1, 2, 4, 8 or 16, or 0 = chosen
+          per frame from the ray count, the head's slot width and the CU count (1 whenever the rays fill the slots).  With S > 1 a
+          slice's columns hold 16 / S (f16 head: 32 / S) rays with S consecutive samples each (csrc/lz_ngp_frame_spp.hip), so a ray needs
+          1 / S of the dependent passes: for tiles, crops and previews, whose rays do not fill the chip.  A launch shape only -- a ray stops
+          exactly at the cap under either `cap`, every output and count is S = 1's bit for bit; state[72] (slices run) differs.  An
+          attribute, changeable between frames; `last_steps_per_pass` is the S the last fused frame ran at.  Measured (DESIGN.md 4.5 has
+          the sweep): a 64^2 tile at 0 (S = 4 / 8 chosen) 0.22 ms f32 and 0.18 ms with the f16 head, against 0.48 / 0.58 at 1 and
+          0.52 / 0.44 for the loop under (8, 8); a 256^2 frame picks 1 and runs as before."""
+
+    STEPS_PER_PASS = (0, 1, 2, 4, 8, 16)
 
     def __init__(self, net, density_bitfield, bound=1.0, cascade=None, grid_size=128, aabb=None, min_near=0.05, budget_factor=1, n_step_cap=8,
-                 mode="loop", cap="reference"):
+                 mode="loop", cap="reference", steps_per_pass=1):
         import math
         if mode not in ("loop", "fused"):
             raise ValueError("mode must be 'loop' or 'fused', not %r" % (mode,))
+        if isinstance(steps_per_pass, bool) or steps_per_pass not in self.STEPS_PER_PASS:
+            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (steps_per_pass,))
+        if mode == "loop" and steps_per_pass != 1:
+            raise ValueError("steps_per_pass is the fused mode's launch shape: mode 'loop' has its own schedule (budget_factor, n_step_cap)")
+        self.steps_per_pass = int(steps_per_pass)
         if cap not in ("reference", "per_ray"):
             raise ValueError("cap must be 'reference' or 'per_ray', not %r" % (cap,))
         if mode == "fused" and cap == "reference" and int(n_step_cap) != 8:
@@ -309,7 +324,15 @@ class HashgridRenderer:
             res["ray_counts"] = b["ray_counts"]
         return res
 
-    # ---- the whole frame as one persistent kernel (csrc/lz_ngp_frame.hip) ----
+    # ---- the whole frame as one persistent kernel (csrc/lz_ngp_frame.hip, csrc/lz_ngp_frame_spp.hip) ----
+    @property
+    def last_steps_per_pass(self):
+        """samples per ray and pass of the last fused frame (what steps_per_pass = 0 chose); None before the first.  Reads the frame's
+        state buffer: waits for the frame."""
+        if self._fbuf is None:
+            return None
+        return int(self._fbuf["state"][13]) or 1      # LZNF_SPP: written by the S > 1 kernels, 0 after the S = 1 kernels
+
     def _fused_buffers(self, N, dev):
         b = self._fbuf
         if b is None or b["N"] != N or b["dev"] != dev:
@@ -348,7 +371,10 @@ class HashgridRenderer:
                 b["cap_ws"] = torch.zeros(need, dtype=torch.int32, device=dev)
             f.cap_mode, f.ray_last, f.cap_ws = 1, p(b["ray_last"]), p(b["cap_ws"])
             f.N_total = N * self.budget_factor        # the ray budget of the schedule the loop runs (renderer.py:513 with budget_factor = 1)
-        call("lz_ngp_frame_render", C.byref(f), None, stream())
+        spp = self.steps_per_pass
+        if isinstance(spp, bool) or spp not in self.STEPS_PER_PASS:
+            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (spp,))
+        call("lz_ngp_frame_render_spp", C.byref(f), int(spp), None, stream())
         self._keep = (bg, rays_o, rays_d)
         res = dict(image=b["out"], image_raw=b["image"], weights_sum=b["weights_sum"], depth=b["depth"], state=b["state"])
         if count_samples:

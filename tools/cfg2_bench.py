@@ -6,7 +6,12 @@ few schedules, next to the operator-API device loop.  tools/cfg2_bench.py [f32|f
     autocast  half tables, half head (precision="f16": the reference's torch-autocast arithmetic)
   --mode loop|fused|both   HashgridRenderer's mode (default loop; fused: csrc/lz_ngp_frame.hip needs n_step_cap 8).  both: loop and
                            fused ALTERNATED, --rounds times each (default 2), every timing listed: the same-box comparison of DESIGN 4.5
-  --max-steps K            (default 128)      --size S   an S x S frame (default 256; 64 = a tile)      --cap reference|per_ray"""
+  --max-steps K            (default 128)      --size S   an S x S frame (default 256; 64 = a tile)      --cap reference|per_ray
+  --steps-per-pass LIST    the fused mode at each steps_per_pass of LIST (1,2,4,8,16; 0 = auto, reported with the S it chose; "entry" = the
+                           S = 1 kernels through lz_ngp_frame_render, the entry without the argument), with --loops also the loop under
+                           (1, 8) and (8, 8): all configurations ALTERNATED in one process, --rounds times each (default 3), every timing
+                           listed.  --size and --max-steps may be comma lists here; --out FILE writes the JSON there as well.  The sweep
+                           behind the auto rule (csrc/lz_ngp_frame_spp.hip): profiles/cfg2_spp_sweep.json"""
 import json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,12 +25,21 @@ def _opt(name, default):
 
 
 rmode, cap = _opt("--mode", "loop"), _opt("--cap", "reference")
-max_steps, size, rounds = int(_opt("--max-steps", 128)), int(_opt("--size", 256)), int(_opt("--rounds", 2))
+spp_list = [x if x == "entry" else int(x) for x in _opt("--steps-per-pass", "").split(",") if x]
+sizes, steps_list = [int(x) for x in str(_opt("--size", 256)).split(",")], [int(x) for x in str(_opt("--max-steps", 128)).split(",")]
+max_steps, size, rounds = steps_list[0], sizes[0], int(_opt("--rounds", 3 if spp_list else 2))
 mode = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("f32", "f16", "autocast") else "f32"
 half = mode in ("f16", "autocast")
 dev = torch.device("cuda", 0)
-pose, intr = synthetic_camera(size, size)
-ro, rd = frame_rays(torch.from_numpy(np.ascontiguousarray(pose)).to(dev), intr, size, size)
+
+
+def rays(n):
+    pose, intr = synthetic_camera(n, n)
+    o, d = frame_rays(torch.from_numpy(np.ascontiguousarray(pose)).to(dev), intr, n, n)
+    return o.reshape(-1, 3).contiguous(), d.reshape(-1, 3).contiguous()
+
+
+ro, rd = rays(size)
 aabb = torch.tensor([-1, -1, -1, 1, 1, 1], dtype=torch.float32, device=dev)
 bits = torch.full((128 ** 3 // 8,), 255, dtype=torch.uint8, device=dev)
 g = GenericHashgridNeRF(dev, half_tables=half)
@@ -42,6 +56,59 @@ def timed(f, n=10):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n * 1e3, o
 
+
+class EntryRenderer(HashgridRenderer):
+    """the fused mode through lz_ngp_frame_render, the entry without steps_per_pass (the S = 1 kernels): what the renderer called before
+    lz_ngp_frame_render_spp existed"""
+
+    def _render_fused(self, *a):
+        import lzzx_nerf_amd.ngp as M
+        real = M.call
+        M.call = lambda name, *args: real("lz_ngp_frame_render", args[0], *args[2:]) if name == "lz_ngp_frame_render_spp" else real(name, *args)
+        try:
+            return super()._render_fused(*a)
+        finally:
+            M.call = real
+
+
+def spp_sweep():
+    """{size: {max_steps: {configuration: {ms: [one per round], S, samples, rows}}}}; a timing is the mean frame time of a window of at
+    least 0.1 s (at least 10 frames) behind a warm-up, host clock around a device synchronise"""
+    res = {}
+    for n in sizes:
+        o, d = rays(n)
+        for ms_cap in steps_list:
+            cfgs = {}
+            for s in spp_list:
+                cls, kw = (EntryRenderer, {}) if s == "entry" else (HashgridRenderer, dict(steps_per_pass=s))
+                cfgs["entry" if s == "entry" else ("auto" if s == 0 else "S%d" % s)] = cls(net, bits, bound=1.0, aabb=aabb, mode="fused", cap=cap, **kw)
+            if "--loops" in sys.argv:
+                for b, c in ((1, 8), (8, 8)):
+                    cfgs["loop_%dx%d" % (b, c)] = HashgridRenderer(net, bits, bound=1.0, aabb=aabb, budget_factor=b, n_step_cap=c)
+            cell = {k: dict(ms=[]) for k in cfgs}
+            for _ in range(rounds):
+                for k, r in cfgs.items():
+                    f = lambda: r.render(o, d, max_steps=ms_cap)
+                    est, _o = timed(f, 5)
+                    t, got = timed(f, max(10, min(2000, int(100.0 / max(est, 1e-3)))))
+                    st = got["state"].cpu().numpy()
+                    cell[k]["ms"].append(round(t, 4))
+                    cell[k].update(samples=int(st[5]), rows=int(st[72]))
+                    if r.mode == "fused":
+                        cell[k]["S"] = r.last_steps_per_pass
+            res.setdefault(str(n), {})[str(ms_cap)] = cell
+            del cfgs
+    return res
+
+
+if spp_list:
+    out = {"mode": mode, "cap": cap, "rounds": rounds, "occupancy": "all ones", "device": torch.cuda.get_device_name(0), "frames": spp_sweep()}
+    line = json.dumps(out)
+    if "--out" in sys.argv:
+        with open(_opt("--out", None), "w") as fh:
+            fh.write(line + "\n")
+    print(line)
+    sys.exit(0)
 
 scheds = [tuple(int(x) for x in a.split(",")) for a in sys.argv[2:] if "," in a] or [(8, 8), (4, 4), (8, 16), (16, 16), (1, 8)]
 out = {"mode": mode, "renderer_mode": rmode, "max_steps": max_steps, "size": size}
