@@ -987,6 +987,31 @@ int lz_ngp_frame_render(const lz_frame_ngp_fused* f, struct lz_timing* timing, l
  * 0 = chosen from N, the head's slot width and the CU count (1 whenever the rays fill the slots).  state [13]: the S of an S > 1
  * launch (0 after the S = 1 kernels).  Anything else: LZ_ERR_BAD_ARGUMENT before any launch.  Additive under ABI version 11. */
 int lz_ngp_frame_render_spp(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, struct lz_timing* timing, lz_stream_t stream);
+/* lz_ngp_frame_render_spp with what lz_frame_render offers next to the frame itself (additive under ABI version 11: new entries only,
+ * lz_frame_ngp_fused keeps its layout).  o == NULL or an all-zero *o: lz_ngp_frame_render_spp, launch for launch.
+ *   noises         the reference's perturb on the frame's first march: every ray starts at near + clamp(near * dt_gamma, dt_min, dt_max) *
+ *                  noises[ray] (raymarching.cu:873) -- lz_ngp_loop_run's frame from lz_perturb_starts' starts, bit for bit
+ *   occupied_aabb  the march is confined to lz_occupied_bounds' box of the occupied cells: the same samples, bit for bit, without a cell
+ *                  test per empty cell in front of and behind the object; t_end receives every ray's clipped march end
+ *   out_rgb24      (uint8_t)(out * 255) per element, written wherever out is
+ *   defer_finish   a TILE of a larger frame under cap_mode 1: f->N_total is the ray budget of the WHOLE frame's schedule, and the call
+ *                  stops behind phase 1 and the histogram of the rays' last surviving chunk boundary, cap_ws[0 .. max_steps].  The caller
+ *                  sums those words over all tiles of the frame, in place (stream order), and calls lz_ngp_frame_finish with the same
+ *                  descriptors: schedule replay (C_eff of the whole frame), phase 2 in phase 1's launch shape, count fix-up.  The tiles then
+ *                  hold the frame's pixels, sums and counts on every ray, whatever S each tile ran at.  Nothing is kept between the two
+ *                  calls: steps_per_pass = 0 resolves through the same rule on the same arguments in both.
+ * LZ_ERR_BAD_ARGUMENT before any launch: occupied_aabb without t_end; defer_finish under cap_mode 0; lz_ngp_frame_finish under cap_mode 0.
+ * N == 0: LZ_OK, nothing launched (with defer_finish the histogram words are zeroed, so an empty tile adds nothing to the sum). */
+typedef struct {
+    const float* noises;           /* [N] or NULL: perturb draws in [0,1), as lz_frame_fused.noises */
+    const float* occupied_aabb;    /* [6] or NULL: lz_occupied_bounds' box; needs t_end */
+    float* t_end;                  /* [N] scratch with occupied_aabb */
+    uint8_t* out_rgb24;            /* [N,3] or NULL */
+    uint32_t defer_finish;         /* cap_mode 1: stop behind phase 1 + the histogram of ray_last (cap_ws[0..max_steps]) */
+} lz_frame_ngp_fused_opts;
+int lz_ngp_frame_render_opts(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, uint32_t steps_per_pass, struct lz_timing* timing,
+                             lz_stream_t stream);
+int lz_ngp_frame_finish(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, uint32_t steps_per_pass, lz_stream_t stream);
 /* ---- Hash-grid NeRF training (lzzx_nerf_amd/ngp_train.py, FusedHashgridTrainNeRF; csrc/lz_ngp_train.hip) ----------------------
  * Additive under ABI version 11: new entries only.  Replaces the backward of sigma_net / color_net under autograd (network.py:73-94:
  * Linear, ReLU, cat with the SH features, exp, sigmoid).  The forward is lz_ngp_head_forward on tiled f32 features (feat_layout 1).

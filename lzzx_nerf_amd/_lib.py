@@ -83,6 +83,11 @@ class FrameNgpFused(C.Structure):
                 ("dt_gamma", f32), ("T_thresh", f32), ("min_near", f32), ("N", u32), ("max_steps", u32), ("C", u32), ("H", u32), ("N_total", u32)]
 
 
+class FrameNgpFusedOpts(C.Structure):
+    """mirror of lz_frame_ngp_fused_opts (include/lzzx_nerf_hip.h)"""
+    _fields_ = [("noises", vp), ("occupied_aabb", vp), ("t_end", vp), ("out_rgb24", vp), ("defer_finish", u32)]
+
+
 class FrameNgp(C.Structure):
     """mirror of lz_frame_ngp (include/lzzx_nerf_hip.h)"""
     _fields_ = [("packed", vp), ("embeddings", vp), ("offsets", vp), ("enc_L", u32), ("enc_H", u32), ("enc_S", f32), ("emb_f16", i32), ("feats", vp),
@@ -155,6 +160,8 @@ SIGNATURES = {
     "lz_ngp_loop_run_f16": [C.POINTER(FrameNgp), vp, u32, u32, vp],
     "lz_ngp_frame_render": [C.POINTER(FrameNgpFused), vp, vp],
     "lz_ngp_frame_render_spp": [C.POINTER(FrameNgpFused), u32, vp, vp],
+    "lz_ngp_frame_render_opts": [C.POINTER(FrameNgpFused), C.POINTER(FrameNgpFusedOpts), u32, vp, vp],
+    "lz_ngp_frame_finish": [C.POINTER(FrameNgpFused), C.POINTER(FrameNgpFusedOpts), u32, vp],
     # hash-grid NeRF training (csrc/lz_ngp_train.hip, lzzx_nerf_amd/ngp_train.py)
     "lz_ngp_head_backward": [vp] * 7 + [u32] + [vp] * 10,
     "lz_timing_create": [u32, C.POINTER(vp)],

@@ -1102,6 +1102,9 @@ void lzf_enqueue_cap_hist(const LzFrameK& K, bool sched, hipStream_t st) {
     if (sched) hipLaunchKernelGGL(lz_k_frame_cap_hist<true>, dim3(hb), dim3(1024), lds, st, K);
     else hipLaunchKernelGGL(lz_k_frame_cap_hist<false>, dim3(hb), dim3(1024), lds, st, K);
 }
+void lzf_enqueue_schedule(const LzFrameK& K, hipStream_t st) {
+    hipLaunchKernelGGL(lz_k_frame_schedule, dim3(1), dim3(256), LZF_SCHED_LDS_INTS((size_t)K.max_steps) * sizeof(int), st, K);
+}
 void lzf_enqueue_counts(const LzFrameK& K, hipStream_t st) {
     hipLaunchKernelGGL(lz_k_frame_counts, dim3(lz_div_up(K.N, 256)), dim3(256), 0, st, K);
 }
@@ -1189,7 +1192,7 @@ static int lzf_launch_persistent(const lz_frame_fused* f, const LzFrameK& K, hip
 static int lzf_finish(const lz_frame_fused* f, hipStream_t st, float* c1sh) {
     LzFrameK K;
     lzf_fill(f, K);
-    if (f->defer_finish) hipLaunchKernelGGL(lz_k_frame_schedule, dim3(1), dim3(256), LZF_SCHED_LDS_INTS(f->max_steps) * sizeof(int), st, K);
+    if (f->defer_finish) lzf_enqueue_schedule(K, st);
     K.phase2 = 1;
     LzfC1Sh own;
     int rc = LZ_OK;

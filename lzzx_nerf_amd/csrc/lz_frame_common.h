@@ -119,6 +119,8 @@ __device__ __forceinline__ void lzf_ray_end(const LzfOut& O, bool ph2, int ray, 
 int lzf_enqueue_queue(const LzFrameK& K, hipStream_t st);
 // cap_mode 1, behind phase 1: histogram of ray_last, parked rays into the queue; sched: the last workgroup replays the schedule (C_eff)
 void lzf_enqueue_cap_hist(const LzFrameK& K, bool sched, hipStream_t st);
+// cap_mode 1, behind a histogram enqueued with sched = false (and summed over the tiles of the frame): the schedule replay on its own
+void lzf_enqueue_schedule(const LzFrameK& K, hipStream_t st);
 // cap_mode 1 with ray_counts, behind phase 2: marched counts of the rays the compositing cut inside a chunk
 void lzf_enqueue_counts(const LzFrameK& K, hipStream_t st);
 #endif

@@ -9,7 +9,10 @@
 // lzn_chain_colour (f32 head, lz_ngp_chain.h) or lzn16_chain (f16 head, lz_ngp16_chain.h) -- a sample's sigma / rgb do not depend on
 // which other samples share its slice -- and the compositing is lz_loop_composite_plain's arithmetic in its order.  Near / far, first
 // occupied cell, background pixels, longest-first queue, the reference's cap (histogram of the last surviving chunk boundary, schedule
-// replay, phase 2 over the parked rays) and the count fix-up are lz_frame.hip's own kernels (lz_frame_common.h).
+// replay, phase 2 over the parked rays) and the count fix-up are lz_frame.hip's own kernels (lz_frame_common.h).  So are the options of
+// lz_ngp_frame_render_opts: perturb draws and the occupied cells' box (lz_k_frame_prepare; the persistent kernels take a ray's march end
+// from t_end then), RGB24 pixels (lzf_write_pixel), and a tile of a larger frame, whose call stops behind the histogram and goes on in
+// lz_ngp_frame_finish once the caller has summed it over the tiles (lz_frame_render / lz_frame_finish with defer_finish).
 //
 // MI355X shape
 //   * A wave owns 16 ray slots with the f32 head (the B-operand columns of a 16x16x4 slice: lane (s, q) gathers levels q, q + 4, q + 8,
@@ -101,7 +104,7 @@ __global__ void __launch_bounds__(LZNF_WG) lz_k_ngp_frame(LzNgpFrameArgs P, LzFr
                         ray = F.order[idx];
                         sloti[NF_RAY * NS + sl] = ray;
                         slot[NF_T * NS + sl] = F.rays_t[ray];
-                        slot[NF_FAR * NS + sl] = F.fars[ray];
+                        slot[NF_FAR * NS + sl] = F.occ ? F.t_end[ray] : F.fars[ray];     // the march's end: clipped to the occupied cells' box
                         if (ph2) {                                   // the accumulators phase 1 parked in the output arrays
                             slot[NF_WS * NS + sl] = F.weights_sum[ray];
                             slot[NF_D * NS + sl] = F.depth[ray];
@@ -322,22 +325,24 @@ static void lznf_launch(int variant, uint32_t N, const LzNgpFrameArgs& a, const 
     else hipLaunchKernelGGL((lz_k_ngp_frame<0, __half>), dim3(grid), dim3(LZNF_WG), 0, st, a, K);
 }
 
-// the frame at `steps_per_pass` samples per ray and pass: 1 = lz_k_ngp_frame, 2 .. 16 = lz_k_ngp_frame_spp, 0 = lznf_spp_auto's choice
-static int lznf_render(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_timing* timing, lz_stream_t stream) {
+// what is refused whatever N is: the descriptor's modes, and the option rules of lz_ngp_frame_render_opts (o may be null)
+static int lznf_check_modes(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o) {
     LZ_REQUIRE(f, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: null");
     LZ_REQUIRE(f->precision == 0 || f->precision == 1, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: precision must be 0 (f32 head) or 1 (f16 head)");
     LZ_REQUIRE(f->cap_mode == LZ_FRAME_CAP_PER_RAY || f->cap_mode == LZ_FRAME_CAP_REFERENCE, LZ_ERR_BAD_ARGUMENT,
                "ngp_frame_render: cap_mode must be 0 (per ray) or 1 (the reference's schedule)");
     if (f->cap_mode == LZ_FRAME_CAP_REFERENCE)
         LZ_REQUIRE(f->max_steps <= LZF_CAP_MAX_STEPS, LZ_ERR_UNSUPPORTED, "ngp_frame_render: cap_mode 1 supports max_steps <= %d", LZF_CAP_MAX_STEPS);
-    hipStream_t st = lz_st(stream);
-    if (f->N == 0) {                                                 // no ray: nothing to launch; a state buffer says "no samples"
-        if (f->state) {
-            const hipError_t e = hipMemsetAsync(f->state, 0, LZ_FRAME_STATE_INTS * sizeof(int32_t), st);
-            if (e != hipSuccess) { lz_set_error("ngp_frame_render: memset: %s", hipGetErrorString(e)); return (int)e; }
-        }
-        return LZ_OK;
+    if (o) {
+        LZ_REQUIRE(!o->occupied_aabb || o->t_end, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render_opts: occupied_aabb needs the t_end scratch buffer");
+        LZ_REQUIRE(!o->defer_finish || f->cap_mode == LZ_FRAME_CAP_REFERENCE, LZ_ERR_BAD_ARGUMENT,
+                   "ngp_frame_render_opts: defer_finish splits the reference's cap (cap_mode 1); cap_mode 0 has no second phase");
     }
+    return LZ_OK;
+}
+
+// the rest of the descriptor, and the two kernel-argument records filled from it (N > 0)
+static int lznf_fill(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, LzNgpFrameArgs& a, LzFrameK& K) {
     LZ_REQUIRE(f->state, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: null state");
     LZ_REQUIRE((f->precision == 1 ? f->packed16 != nullptr : f->packed != nullptr) && f->embeddings && f->offsets, LZ_ERR_BAD_ARGUMENT,
                "ngp_frame_render: incomplete network (packed for precision 0, packed16 for precision 1, embeddings, offsets)");
@@ -351,13 +356,11 @@ static int lznf_render(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_
         LZ_REQUIRE(f->ray_last && f->cap_ws, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: cap_mode 1 needs the ray_last and cap_ws buffers");
         LZ_REQUIRE(f->N_total == 0 || f->N_total >= f->N, LZ_ERR_BAD_ARGUMENT, "ngp_frame_render: N_total is the schedule's ray budget (>= N)");
     }
-    LzNgpFrameArgs a;
     a.packed = f->precision == 1 ? f->packed16 : static_cast<const void*>(f->packed);
     a.emb = f->embeddings;
     a.offsets = f->offsets;
     a.inv2b = 1.0f / (2.0f * f->bound);
     LZ_REQUIRE(lz_fill_levels(a.lv, f->enc_L, f->enc_S, f->enc_H) == 0, LZ_ERR_UNSUPPORTED, "ngp_frame_render: at most %d levels", LZ_MAX_LEVELS);
-    LzFrameK K;
     memset(&K, 0, sizeof(K));
     K.rays_o = f->rays_o; K.rays_d = f->rays_d; K.grid = f->grid; K.aabb = f->aabb;
     K.nears = f->nears; K.fars = f->fars; K.rays_t = f->rays_t;
@@ -369,32 +372,102 @@ static int lznf_render(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_
     K.N = f->N; K.max_steps = f->max_steps; K.C = f->C; K.H = f->H;
     K.ray_last = f->ray_last; K.cap_ws = f->cap_ws; K.cap_mode = f->cap_mode; K.phase2 = 0; K.N_total = f->N_total;
     K.mf = lz_march_frame(f->bound, f->max_steps, f->C, f->H);
-    const int variant = f->precision == 1 ? 1 : (f->emb_f16 ? 2 : 0);
+    if (o) {                                                         // lz_ngp_frame_render_opts: what lz_k_frame_prepare and lzf_write_pixel already do
+        K.noises = o->noises;
+        K.occ = o->occupied_aabb; K.t_end = o->t_end;
+        K.out_rgb24 = o->out_rgb24;
+    }
+    return LZ_OK;
+}
+
+static int lznf_variant(const lz_frame_ngp_fused* f) { return f->precision == 1 ? 1 : (f->emb_f16 ? 2 : 0); }
+
+// the persistent kernel over the queue (phase 1) or over the rays parked at the cap (K.phase2), S samples per ray and pass
+static void lznf_launch_persistent(int variant, uint32_t S, uint32_t N, const LzNgpFrameArgs& a, const LzFrameK& K, hipStream_t st) {
+    if (S == 1) lznf_launch(variant, N, a, K, st);
+    else lznf_spp_launch(variant, S, N, a, K, st);
+}
+
+// the frame at `steps_per_pass` samples per ray and pass: 1 = lz_k_ngp_frame, 2 .. 16 = lz_k_ngp_frame_spp, 0 = lznf_spp_auto's choice
+static int lznf_render(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, uint32_t steps_per_pass, lz_timing* timing, lz_stream_t stream) {
+    int rc = lznf_check_modes(f, o);
+    if (rc != LZ_OK) return rc;
+    hipStream_t st = lz_st(stream);
+    const bool defer = o && o->defer_finish;
+    if (f->N == 0) {                                                 // no ray: nothing to launch; a state buffer says "no samples"
+        hipError_t e = hipSuccess;
+        if (f->state) e = hipMemsetAsync(f->state, 0, LZ_FRAME_STATE_INTS * sizeof(int32_t), st);
+        // an empty tile of a larger frame: its words of the histogram the caller sums over the tiles read zero
+        if (e == hipSuccess && defer && f->cap_ws) e = hipMemsetAsync(f->cap_ws, 0, LZ_FRAME_CAP_WS_INTS((size_t)f->max_steps) * sizeof(int32_t), st);
+        if (e != hipSuccess) { lz_set_error("ngp_frame_render: memset: %s", hipGetErrorString(e)); return (int)e; }
+        return LZ_OK;
+    }
+    LzNgpFrameArgs a;
+    LzFrameK K;
+    rc = lznf_fill(f, o, a, K);
+    if (rc != LZ_OK) return rc;
+    const int variant = lznf_variant(f);
     const uint32_t S = steps_per_pass ? steps_per_pass : lznf_spp_auto(variant, f->N, f->max_steps);
-    int rc = lzf_enqueue_queue(K, st);                               // memset + prepare + scatter (lz_frame.hip)
+    rc = lzf_enqueue_queue(K, st);                                   // memset + prepare + scatter (lz_frame.hip)
     if (rc != LZ_OK) return rc;
     if (timing) (void)lz_timing_mark(timing, 0, stream);             // the event pair brackets the phase-1 persistent kernel alone
-    if (S == 1) lznf_launch(variant, f->N, a, K, st);
-    else lznf_spp_launch(variant, S, f->N, a, K, st);
+    lznf_launch_persistent(variant, S, f->N, a, K, st);
     if (timing) (void)lz_timing_mark(timing, 1, stream);
     if (f->cap_mode == LZ_FRAME_CAP_REFERENCE) {
-        lzf_enqueue_cap_hist(K, true, st);                           // histogram of ray_last, parked rays queued, schedule replay: C_eff
-        K.phase2 = 1;
-        // the parked rays up to C_eff (an early-out launch when none), in phase 1's launch shape: N bounds their number
-        if (S == 1) lznf_launch(variant, f->N, a, K, st);
-        else lznf_spp_launch(variant, S, f->N, a, K, st);
-        if (f->ray_counts) lzf_enqueue_counts(K, st);
+        // histogram of ray_last, parked rays queued; a whole frame also replays the schedule there (C_eff), a tile leaves that to
+        // lz_ngp_frame_finish, behind the caller's sum of the histogram over the tiles
+        lzf_enqueue_cap_hist(K, !defer, st);
+        if (!defer) {
+            K.phase2 = 1;
+            // the parked rays up to C_eff (an early-out launch when none), in phase 1's launch shape: N bounds their number
+            lznf_launch_persistent(variant, S, f->N, a, K, st);
+            if (f->ray_counts) lzf_enqueue_counts(K, st);
+        }
     }
     LZ_CHECK_LAUNCH("ngp_frame_render");
     return LZ_OK;
 }
 
+static bool lznf_spp_valid(uint32_t S) { return S == 0 || S == 1 || S == 2 || S == 4 || S == 8 || S == 16; }
+
 extern "C" int lz_ngp_frame_render(const lz_frame_ngp_fused* f, lz_timing* timing, lz_stream_t stream) {
-    return lznf_render(f, 1, timing, stream);
+    return lznf_render(f, nullptr, 1, timing, stream);
 }
 
 extern "C" int lz_ngp_frame_render_spp(const lz_frame_ngp_fused* f, uint32_t steps_per_pass, lz_timing* timing, lz_stream_t stream) {
-    LZ_REQUIRE(steps_per_pass == 0 || steps_per_pass == 1 || steps_per_pass == 2 || steps_per_pass == 4 || steps_per_pass == 8 || steps_per_pass == 16,
-               LZ_ERR_BAD_ARGUMENT, "ngp_frame_render_spp: steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %u", steps_per_pass);
-    return lznf_render(f, steps_per_pass, timing, stream);
+    LZ_REQUIRE(lznf_spp_valid(steps_per_pass), LZ_ERR_BAD_ARGUMENT, "ngp_frame_render_spp: steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %u",
+               steps_per_pass);
+    return lznf_render(f, nullptr, steps_per_pass, timing, stream);
+}
+
+extern "C" int lz_ngp_frame_render_opts(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, uint32_t steps_per_pass, lz_timing* timing,
+                                        lz_stream_t stream) {
+    LZ_REQUIRE(lznf_spp_valid(steps_per_pass), LZ_ERR_BAD_ARGUMENT, "ngp_frame_render_opts: steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %u",
+               steps_per_pass);
+    return lznf_render(f, o, steps_per_pass, timing, stream);
+}
+
+// the second half of a frame begun with defer_finish, behind the caller's sum of cap_ws[0 .. max_steps] over the tiles: the schedule replay
+// (C_eff, the chunk boundaries), phase 2 in phase 1's launch shape -- S from the same rule on the same arguments: nothing is kept between
+// the two calls -- and the count fix-up.  lz_frame_finish is the model.
+extern "C" int lz_ngp_frame_finish(const lz_frame_ngp_fused* f, const lz_frame_ngp_fused_opts* o, uint32_t steps_per_pass, lz_stream_t stream) {
+    LZ_REQUIRE(lznf_spp_valid(steps_per_pass), LZ_ERR_BAD_ARGUMENT, "ngp_frame_finish: steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %u",
+               steps_per_pass);
+    int rc = lznf_check_modes(f, o);
+    if (rc != LZ_OK) return rc;
+    LZ_REQUIRE(f->cap_mode == LZ_FRAME_CAP_REFERENCE, LZ_ERR_BAD_ARGUMENT, "ngp_frame_finish: only after lz_ngp_frame_render_opts with cap_mode 1");
+    if (f->N == 0) return LZ_OK;                                     // an empty tile
+    LzNgpFrameArgs a;
+    LzFrameK K;
+    rc = lznf_fill(f, o, a, K);
+    if (rc != LZ_OK) return rc;
+    hipStream_t st = lz_st(stream);
+    const int variant = lznf_variant(f);
+    const uint32_t S = steps_per_pass ? steps_per_pass : lznf_spp_auto(variant, f->N, f->max_steps);
+    lzf_enqueue_schedule(K, st);
+    K.phase2 = 1;
+    lznf_launch_persistent(variant, S, f->N, a, K, st);
+    if (f->ray_counts) lzf_enqueue_counts(K, st);
+    LZ_CHECK_LAUNCH("ngp_frame_finish");
+    return LZ_OK;
 }

@@ -48,7 +48,7 @@ __device__ __forceinline__ void lznf_take_ray(const LzFrameK& F, bool ph2, int r
     int* sloti = reinterpret_cast<int*>(slot);
     sloti[NF_RAY * NS + sl] = ray;
     slot[NF_T * NS + sl] = F.rays_t[ray];
-    slot[NF_FAR * NS + sl] = F.fars[ray];
+    slot[NF_FAR * NS + sl] = F.occ ? F.t_end[ray] : F.fars[ray];     // the march's end: clipped to the occupied cells' box
     if (ph2) {                                   // the accumulators phase 1 parked in the output arrays
         slot[NF_WS * NS + sl] = F.weights_sum[ray];
         slot[NF_D * NS + sl] = F.depth[ray];

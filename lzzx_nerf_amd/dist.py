@@ -266,7 +266,7 @@ class ShardedFrame:
 
     def __init__(self, H, W, rank, world, tiles="contiguous", device="cuda", channels=3, dtype=torch.float32, group=None,
                  steps_per_pass=None, via="collective", cap="reference"):
-        """cap (`configure(renderer)` applies it to a fused TriplaneRenderer): the reference stops every ray that is still alive at
+        """cap (`configure(renderer)` applies it to a fused TriplaneRenderer or ngp.HashgridRenderer): the reference stops every ray that is still alive at
         `max_steps` after the same FRAME-WIDE count C_eff = the sum of its loop's n_step = max(min(N // n_alive, 8), 1)
         (renderer.py:503-548) -- N and n_alive being those of the whole frame.
           "reference": the tiles reproduce that: every rank histograms its rays' last surviving chunk boundary, the max_steps + 1 int32
@@ -299,7 +299,8 @@ class ShardedFrame:
         return hist
 
     def configure(self, renderer):
-        """apply the cap rule and the pinned launch shape (if any) to a TriplaneRenderer; returns it"""
+        """apply the cap rule and the pinned launch shape (if any) to a fused TriplaneRenderer or ngp.HashgridRenderer (both are driven
+        by these attributes); returns it"""
         if self.steps_per_pass is not None:
             renderer.steps_per_pass = int(self.steps_per_pass)
         renderer.cap = self.cap

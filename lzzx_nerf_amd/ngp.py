@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._util import call, ptr, stream
-from .renderer import MAX_RAYS_PER_PASS, _STATE_INTS, _N_SAMPLES_OFF   # noqa: F401
+from .renderer import MAX_RAYS_PER_PASS, _STATE_INTS, _N_SAMPLES_OFF, TriplaneRenderer   # noqa: F401
 
 NGP_FRAGS = 96          # LZ_NGP_FRAGS
 TILE_ROWS = 256         # LZ_GRID_TILE_ROWS
@@ -213,12 +213,23 @@ class HashgridRenderer:
           exactly at the cap under either `cap`, every output and count is S = 1's bit for bit; state[72] (slices run) differs.  An
           attribute, changeable between frames; `last_steps_per_pass` is the S the last fused frame ran at.  Measured (DESIGN.md 4.5 has
           the sweep): a 64^2 tile at 0 (S = 4 / 8 chosen) 0.22 ms f32 and 0.18 ms with the f16 head, against 0.48 / 0.58 at 1 and
-          0.52 / 0.44 for the loop under (8, 8); a 256^2 frame picks 1 and runs as before."""
+          0.52 / 0.44 for the loop under (8, 8); a 256^2 frame picks 1 and runs as before.
+        Next to the frame, all opt-in (csrc/lz_ngp_frame.hip: lz_ngp_frame_render_opts / lz_ngp_frame_finish; with none in use the
+        launches are those of before):
+          tiles of ONE frame under cap "reference": `frame_rays_total` (the frame's ray count) and `cap_exchange` (a callable that sums
+            the [max_steps + 1] int32 histogram over the tiles in place) -- dist.ShardedFrame.configure sets both -- or fused_begin /
+            fused_finish around the caller's own sum.  A ray alive at the cap receives C_eff samples of the FRAME-wide schedule; a tile
+            rendered on its own replays the schedule with its own ray counts and differs on exactly those rays.  With these the tiles
+            are the frame's pixels, sums and counts on every ray, whatever steps_per_pass each tile runs at.
+          `clip_to_occupancy` (default False; constructor argument and attribute), `occupancy_margin`, occupied_bounds(),
+            invalidate_occupancy(): TriplaneRenderer's -- the march confined to the box of the occupied cells, the same samples bit
+            for bit (256^2 ellipsoid frame 0.286 -> 0.258 ms; all-ones occupancy: no difference).
+          render(..., perturb=True[, noises=u]) and render(..., rgb24=True): both modes, the same bits in both."""
 
     STEPS_PER_PASS = (0, 1, 2, 4, 8, 16)
 
     def __init__(self, net, density_bitfield, bound=1.0, cascade=None, grid_size=128, aabb=None, min_near=0.05, budget_factor=1, n_step_cap=8,
-                 mode="loop", cap="reference", steps_per_pass=1):
+                 mode="loop", cap="reference", steps_per_pass=1, clip_to_occupancy=False):
         import math
         if mode not in ("loop", "fused"):
             raise ValueError("mode must be 'loop' or 'fused', not %r" % (mode,))
@@ -227,6 +238,8 @@ class HashgridRenderer:
         if mode == "loop" and steps_per_pass != 1:
             raise ValueError("steps_per_pass is the fused mode's launch shape: mode 'loop' has its own schedule (budget_factor, n_step_cap)")
         self.steps_per_pass = int(steps_per_pass)
+        if mode == "loop" and clip_to_occupancy:
+            raise ValueError("clip_to_occupancy belongs to mode 'fused': the loop's march kernels test every cell")
         if cap not in ("reference", "per_ray"):
             raise ValueError("cap must be 'reference' or 'per_ray', not %r" % (cap,))
         if mode == "fused" and cap == "reference" and int(n_step_cap) != 8:
@@ -246,6 +259,18 @@ class HashgridRenderer:
         self.chunk, self.lookahead = 4, 2
         self._buf = None
         self._fbuf = None
+        # fused mode, cap "reference", when this renderer draws a TILE of a frame: the frame's ray count (the N of renderer.py:513) and a
+        # callable that sums the [max_steps + 1] int32 histogram over the tiles in place (dist.ShardedFrame.configure sets both)
+        self.frame_rays_total = None
+        self.cap_exchange = None
+        # fused mode: confine every ray's march to the bounds of the occupied cells (lz_occupied_bounds): same samples, bit for bit
+        self.clip_to_occupancy = bool(clip_to_occupancy)
+        self.occupancy_margin = 8      # cells; see occupied_bounds()
+        self._occ = None
+
+    # the cached box of the occupied cells: TriplaneRenderer's rule (tensor identity plus version) on this renderer's bitfield
+    occupied_bounds = TriplaneRenderer.occupied_bounds
+    invalidate_occupancy = TriplaneRenderer.invalidate_occupancy
 
     def _buffers(self, N, dev):
         rows = max(N * self.budget_factor, N)
@@ -263,23 +288,40 @@ class HashgridRenderer:
         return b
 
     @torch.no_grad()
-    def render(self, rays_o, rays_d, dt_gamma=1.0 / 256, max_steps=128, T_thresh=1e-4, bg_color=1.0, count_samples=False):
-        """-> dict(image [N,3] blended + clamped, image_raw, weights_sum, depth, state, ray_counts if requested); ready in stream order"""
+    def render(self, rays_o, rays_d, dt_gamma=1.0 / 256, max_steps=128, T_thresh=1e-4, bg_color=1.0, count_samples=False, rgb24=False,
+               perturb=False, noises=None):
+        """-> dict(image [N,3] blended + clamped, image_raw, weights_sum, depth, state, ray_counts if requested, image_rgb24 [N,3] uint8
+        with rgb24: the video pipe's hand-off format, quantised on the device); ready in stream order.
+        perturb: the reference's inference loop passes `perturb` to march_rays on its FIRST iteration only (renderer.py:344,521), where
+        every ray's start moves by clamp(near * dt_gamma, dt_min, dt_max) * U[0,1) (raymarching.cu:873).  `noises` [N] supplies the draws
+        (tests; default torch.rand like raymarching.py:298).  Both modes, the same bits."""
         rays_o = rays_o.reshape(-1, 3).float().contiguous()
         rays_d = rays_d.reshape(-1, 3).float().contiguous()
         N, dev = rays_o.shape[0], rays_o.device
+        if perturb and noises is None:
+            noises = torch.rand(N, dtype=torch.float32, device=dev)
+        if noises is not None:
+            noises = noises.reshape(-1).to(dev, torch.float32).contiguous()
+            if noises.numel() != N:
+                raise RuntimeError("noises must hold one value per ray")
         if N > MAX_RAYS_PER_PASS:
             raise RuntimeError("HashgridRenderer renders at most %d rays per call" % MAX_RAYS_PER_PASS)
-        if N == 0:
+        tile = self.mode == "fused" and self.cap == "reference" and self.frame_rays_total is not None
+        if N == 0 and not tile:       # (an empty tile of a larger frame still takes part in the exchange of the histogram)
             from .renderer import _empty_result
-            return _empty_result(dev, count_samples, ambient=False)
+            return _empty_result(dev, count_samples, rgb24, ambient=False)
         if self.mode == "fused":
-            return self._render_fused(rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples)
+            return self._render_fused(rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24, noises)
         b = self._buffers(N, dev)
         call("lz_near_far_from_aabb", ptr(rays_o), ptr(rays_d), ptr(self.aabb), N, self.min_near, ptr(b["nears"]), ptr(b["fars"]), stream())
         if count_samples:
             b["ray_counts"].zero_()
-        call("lz_loop_begin", N, int(max_steps), N * self.budget_factor, self.n_step_cap, ptr(b["nears"]), ptr(b["rays_alive"][0]), ptr(b["rays_t"]),
+        starts = b["nears"]
+        if noises is not None:    # the loop's first march starts every ray at its perturbed t (lz_loop_begin copies `starts` into rays_t)
+            starts = torch.empty_like(b["nears"])
+            call("lz_perturb_starts", ptr(b["nears"]), ptr(noises), float(dt_gamma), int(max_steps), int(self.cascade), int(self.grid_size), N, ptr(starts),
+                 stream())
+        call("lz_loop_begin", N, int(max_steps), N * self.budget_factor, self.n_step_cap, ptr(starts), ptr(b["rays_alive"][0]), ptr(b["rays_t"]),
              ptr(b["weights_sum"]), ptr(b["depth"]), ptr(b["image"]), None, None, None, ptr(b["state"]), ptr(b["workspace"]), stream())
         net, e = self.net, self.net.encoder
         f = _lib.FrameNgp()
@@ -317,11 +359,19 @@ class HashgridRenderer:
                 if int(slot_old[3]) == 1:
                     break
         bg = bg_color.to(dev, torch.float32).expand(N, 3).contiguous() if torch.is_tensor(bg_color) else None
-        call("lz_final_blend", ptr(b["image"]), ptr(b["weights_sum"]), ptr(bg), 1.0 if bg is not None else float(bg_color), N, ptr(b["out"]), stream())
-        self._keep = (bg, rays_o, rays_d)
+        bg_scalar = 1.0 if bg is not None else float(bg_color)
+        if rgb24:
+            if b.get("out_rgb24") is None:
+                b["out_rgb24"] = torch.empty(N, 3, dtype=torch.uint8, device=dev)
+            call("lz_final_blend_rgb24", ptr(b["image"]), ptr(b["weights_sum"]), ptr(bg), bg_scalar, N, ptr(b["out"]), ptr(b["out_rgb24"]), stream())
+        else:
+            call("lz_final_blend", ptr(b["image"]), ptr(b["weights_sum"]), ptr(bg), bg_scalar, N, ptr(b["out"]), stream())
+        self._keep = (bg, rays_o, rays_d, noises)
         res = dict(image=b["out"], image_raw=b["image"], weights_sum=b["weights_sum"], depth=b["depth"], state=b["state"])
         if count_samples:
             res["ray_counts"] = b["ray_counts"]
+        if rgb24:
+            res["image_rgb24"] = b["out_rgb24"]
         return res
 
     # ---- the whole frame as one persistent kernel (csrc/lz_ngp_frame.hip, csrc/lz_ngp_frame_spp.hip) ----
@@ -341,12 +391,38 @@ class HashgridRenderer:
             b = dict(N=N, dev=dev, nears=torch.empty(N, **f), fars=torch.empty(N, **f), rays_t=torch.empty(N, **f), order=torch.empty(N, **i),
                      state=torch.zeros(1024, **i), keys=torch.empty(N, dtype=torch.uint8, device=dev), scratch=torch.empty(N, **f),
                      weights_sum=torch.empty(N, **f), depth=torch.empty(N, **f), image=torch.empty(N, 3, **f), out=torch.empty(N, 3, **f),
-                     ray_counts=None, ray_last=torch.empty(N, **i), cap_ws=None)
+                     ray_counts=None, ray_last=torch.empty(N, **i), cap_ws=None, t_end=None, out_rgb24=None)
             self._fbuf = b
         return b
 
-    def _render_fused(self, rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples):
+    def _render_fused(self, rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24=False, noises=None):
+        ctx = self.fused_begin(rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24, noises)
+        if ctx["deferred"] and self.cap_exchange is not None:
+            self.cap_exchange(ctx["hist"])
+        return self.fused_finish(ctx)
+
+    def fused_begin(self, rays_o, rays_d, dt_gamma=1.0 / 256, max_steps=128, T_thresh=1e-4, bg_color=1.0, count_samples=False, rgb24=False,
+                    noises=None):
+        """Fused mode in two calls, for callers that render tiles of ONE frame under cap = "reference" (TriplaneRenderer.fused_begin's
+        contract): with `frame_rays_total` set to the frame's ray count, fused_begin enqueues phase 1 and the histogram of the rays' last
+        surviving chunk boundary -- ctx["hist"], int32 [max_steps + 1] on the device; the caller sums it over all tiles of the frame, in
+        place -- and fused_finish(ctx) enqueues the schedule replay (ray budget frame_rays_total * budget_factor), phase 2 and the count
+        fix-up and returns the result dict.  The tiles then hold the whole frame's pixels on every ray, whatever steps_per_pass each ran
+        at.  With frame_rays_total unset (a whole frame) and for cap = "per_ray" everything happens in fused_begin."""
+        if self.mode != "fused":
+            raise RuntimeError("fused_begin / fused_finish belong to mode 'fused'")
+        spp = self.steps_per_pass
+        if isinstance(spp, bool) or spp not in self.STEPS_PER_PASS:
+            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (spp,))
+        rays_o = rays_o.reshape(-1, 3).float().contiguous()
+        rays_d = rays_d.reshape(-1, 3).float().contiguous()
         N, dev = rays_o.shape[0], rays_o.device
+        if N > MAX_RAYS_PER_PASS:
+            raise RuntimeError("HashgridRenderer renders at most %d rays per call" % MAX_RAYS_PER_PASS)
+        if noises is not None:
+            noises = noises.reshape(-1).to(dev, torch.float32).contiguous()
+            if noises.numel() != N:
+                raise RuntimeError("noises must hold one value per ray")
         b = self._fused_buffers(N, dev)
         net, e = self.net, self.net.encoder
         if count_samples and b["ray_counts"] is None:
@@ -371,12 +447,37 @@ class HashgridRenderer:
                 b["cap_ws"] = torch.zeros(need, dtype=torch.int32, device=dev)
             f.cap_mode, f.ray_last, f.cap_ws = 1, p(b["ray_last"]), p(b["cap_ws"])
             f.N_total = N * self.budget_factor        # the ray budget of the schedule the loop runs (renderer.py:513 with budget_factor = 1)
-        spp = self.steps_per_pass
-        if isinstance(spp, bool) or spp not in self.STEPS_PER_PASS:
-            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (spp,))
-        call("lz_ngp_frame_render_spp", C.byref(f), int(spp), None, stream())
-        self._keep = (bg, rays_o, rays_d)
+        # the options next to the frame: none in use -> no record, and the call is lz_ngp_frame_render_spp launch for launch
+        o, deferred = _lib.FrameNgpFusedOpts(), False
+        if noises is not None:
+            o.noises = p(noises)
+        if self.clip_to_occupancy:
+            if b["t_end"] is None:
+                b["t_end"] = torch.empty(N, dtype=torch.float32, device=dev)
+            o.occupied_aabb, o.t_end = p(self.occupied_bounds()), p(b["t_end"])
+        if rgb24:
+            if b["out_rgb24"] is None:
+                b["out_rgb24"] = torch.empty(N, 3, dtype=torch.uint8, device=dev)
+            o.out_rgb24 = p(b["out_rgb24"])
+        if self.cap == "reference" and self.frame_rays_total is not None:
+            if int(self.frame_rays_total) < N:
+                raise ValueError("frame_rays_total is the ray count of the whole frame (>= the rays of this call)")
+            f.N_total, o.defer_finish = int(self.frame_rays_total) * self.budget_factor, 1
+            deferred = True
+        used = noises is not None or self.clip_to_occupancy or rgb24 or deferred
+        call("lz_ngp_frame_render_opts", C.byref(f), C.byref(o) if used else None, int(spp), None, stream())
+        keep = (bg, rays_o, rays_d, noises)
+        self._keep = keep
+        return dict(f=f, o=o if used else None, spp=int(spp), b=b, keep=keep, deferred=deferred, count_samples=count_samples, rgb24=rgb24,
+                    hist=b["cap_ws"][: int(max_steps) + 1] if deferred else None)
+
+    def fused_finish(self, ctx):
+        b = ctx["b"]
+        if ctx["deferred"]:
+            call("lz_ngp_frame_finish", C.byref(ctx["f"]), C.byref(ctx["o"]), ctx["spp"], stream())
         res = dict(image=b["out"], image_raw=b["image"], weights_sum=b["weights_sum"], depth=b["depth"], state=b["state"])
-        if count_samples:
+        if ctx["count_samples"]:
             res["ray_counts"] = b["ray_counts"]
+        if ctx["rgb24"]:
+            res["image_rgb24"] = b["out_rgb24"]
         return res

@@ -171,7 +171,7 @@ class FusedHashgridTrainNeRF(nn.Module):
 
     def to_inference(self, precision="f32", mode=None, **renderer):
         """an `ngp.FusedHashgridNeRF` on the current weights (renders through `ngp.HashgridRenderer`); its table is the live parameter.
-        With `mode` ("loop" / "fused") or renderer arguments (density_bitfield=..., bound=..., cap=..., steps_per_pass=...): the
+        With `mode` ("loop" / "fused") or renderer arguments (density_bitfield=..., bound=..., cap=..., steps_per_pass=..., clip_to_occupancy=...): the
         `ngp.HashgridRenderer` of that network in that mode instead."""
         net = FusedHashgridNeRF(self.encoder, self.sigma_net, self.color_net, precision=precision)
         if mode is None and not renderer:

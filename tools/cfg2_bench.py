@@ -11,7 +11,12 @@ few schedules, next to the operator-API device loop.  tools/cfg2_bench.py [f32|f
                            S = 1 kernels through lz_ngp_frame_render, the entry without the argument), with --loops also the loop under
                            (1, 8) and (8, 8): all configurations ALTERNATED in one process, --rounds times each (default 3), every timing
                            listed.  --size and --max-steps may be comma lists here; --out FILE writes the JSON there as well.  The sweep
-                           behind the auto rule (csrc/lz_ngp_frame_spp.hip): profiles/cfg2_spp_sweep.json"""
+                           behind the auto rule (csrc/lz_ngp_frame_spp.hip): profiles/cfg2_spp_sweep.json
+  --clip                   the fused mode with clip_to_occupancy off and on, ALTERNATED in one process, --rounds times each (default 3),
+                           every timing listed, on --occupancy ones (default) or ellipsoid (synthetic.ellipsoid_bitfield_device); --size
+                           and --max-steps may be comma lists, --steps-per-pass one value (default 1), --out FILE as above.  Per cell also
+                           `within`: clip on's mean exceeds clip off's by no more than clip off's own max - min (the A/B rule of DESIGN 4.4)
+                           and `same`: the two frames are equal bit for bit.  profiles/cfg2_clip_bench.json"""
 import json, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +32,7 @@ def _opt(name, default):
 rmode, cap = _opt("--mode", "loop"), _opt("--cap", "reference")
 spp_list = [x if x == "entry" else int(x) for x in _opt("--steps-per-pass", "").split(",") if x]
 sizes, steps_list = [int(x) for x in str(_opt("--size", 256)).split(",")], [int(x) for x in str(_opt("--max-steps", 128)).split(",")]
-max_steps, size, rounds = steps_list[0], sizes[0], int(_opt("--rounds", 3 if spp_list else 2))
+max_steps, size, rounds = steps_list[0], sizes[0], int(_opt("--rounds", 3 if spp_list or "--clip" in sys.argv else 2))
 mode = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("f32", "f16", "autocast") else "f32"
 half = mode in ("f16", "autocast")
 dev = torch.device("cuda", 0)
@@ -64,7 +69,8 @@ class EntryRenderer(HashgridRenderer):
     def _render_fused(self, *a):
         import lzzx_nerf_amd.ngp as M
         real = M.call
-        M.call = lambda name, *args: real("lz_ngp_frame_render", args[0], *args[2:]) if name == "lz_ngp_frame_render_spp" else real(name, *args)
+        # (f, no options, steps_per_pass, timing, stream) -> (f, timing, stream)
+        M.call = lambda name, *args: real("lz_ngp_frame_render", args[0], *args[3:]) if name == "lz_ngp_frame_render_opts" else real(name, *args)
         try:
             return super()._render_fused(*a)
         finally:
@@ -100,6 +106,52 @@ def spp_sweep():
             del cfgs
     return res
 
+
+def clip_sweep():
+    """{size: {max_steps: {"off" | "on": {ms: [one per round], samples, rows}, within, same}}}; timings as spp_sweep's"""
+    res = {}
+    S = spp_list[0] if spp_list else 1
+    for n in sizes:
+        o, d = rays(n)
+        for ms_cap in steps_list:
+            cfgs = {k: HashgridRenderer(net, clip_bits, bound=1.0, aabb=aabb, mode="fused", cap=cap, steps_per_pass=S, clip_to_occupancy=k == "on")
+                    for k in ("off", "on")}
+            cell = {k: dict(ms=[]) for k in cfgs}
+            frames = {}
+            for _ in range(rounds):
+                for k, r in cfgs.items():
+                    f = lambda: r.render(o, d, max_steps=ms_cap)
+                    est, _o = timed(f, 5)
+                    t, got = timed(f, max(10, min(2000, int(100.0 / max(est, 1e-3)))))
+                    st = got["state"].cpu().numpy()
+                    cell[k]["ms"].append(round(t, 4))
+                    cell[k].update(samples=int(st[5]), rows=int(st[72]), S=r.last_steps_per_pass)
+                    frames[k] = {q: got[q].clone() for q in ("image", "image_raw", "weights_sum", "depth")}
+            off, on = cell["off"]["ms"], cell["on"]["ms"]
+            cell["within"] = bool(sum(on) / len(on) - sum(off) / len(off) <= max(off) - min(off))
+            cell["same"] = all(torch.equal(frames["off"][q], frames["on"][q]) for q in frames["off"]) and cell["off"]["samples"] == cell["on"]["samples"]
+            res.setdefault(str(n), {})[str(ms_cap)] = cell
+            del cfgs
+    return res
+
+
+if "--clip" in sys.argv:
+    occupancy = _opt("--occupancy", "ones")
+    if occupancy not in ("ones", "ellipsoid"):
+        sys.exit("--occupancy ones|ellipsoid")
+    if occupancy == "ellipsoid":
+        from lzzx_nerf_amd.synthetic import ellipsoid_bitfield_device
+        clip_bits = ellipsoid_bitfield_device(dev)[0]
+    else:
+        clip_bits = bits
+    out = {"mode": mode, "cap": cap, "rounds": rounds, "occupancy": "all ones" if occupancy == "ones" else "ellipsoid", "device": torch.cuda.get_device_name(0),
+           "frames": clip_sweep()}
+    line = json.dumps(out)
+    if "--out" in sys.argv:
+        with open(_opt("--out", None), "w") as fh:
+            fh.write(line + "\n")
+    print(line)
+    sys.exit(0)
 
 if spp_list:
     out = {"mode": mode, "cap": cap, "rounds": rounds, "occupancy": "all ones", "device": torch.cuda.get_device_name(0), "frames": spp_sweep()}
