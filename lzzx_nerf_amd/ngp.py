@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._util import call, ptr, stream
-from .renderer import MAX_RAYS_PER_PASS, _STATE_INTS, _N_SAMPLES_OFF, TriplaneRenderer   # noqa: F401
+from .renderer import MAX_RAYS_PER_PASS, _STATE_INTS, _N_SAMPLES_OFF, RayRenderer, TriplaneRenderer, _empty_result   # noqa: F401
 
 NGP_FRAGS = 96          # LZ_NGP_FRAGS
 TILE_ROWS = 256         # LZ_GRID_TILE_ROWS
@@ -187,7 +187,7 @@ class FusedHashgridNeRF:
              e.num_levels, self.S, e.base_resolution, 0, 0, int(self.half_tables), stream())
 
 
-class HashgridRenderer:
+class HashgridRenderer(RayRenderer):
     """Inference renderer of one FusedHashgridNeRF + occupancy bitfield: the reference's loop (renderer.py:495-548: march n_step samples per
     alive ray, network, composite_rays, drop dead rays, n_step = max(min(budget_factor * N // n_alive, n_step_cap), 1), stop at max_steps)
     with the state on the device; (budget_factor, n_step_cap) = (1, 8) is the reference's schedule -- same pixels under any schedule for
@@ -227,65 +227,33 @@ class HashgridRenderer:
           render(..., perturb=True[, noises=u]) and render(..., rgb24=True): both modes, the same bits in both."""
 
     STEPS_PER_PASS = (0, 1, 2, 4, 8, 16)
+    FusedDescriptor = _lib.FrameNgpFused
 
     def __init__(self, net, density_bitfield, bound=1.0, cascade=None, grid_size=128, aabb=None, min_near=0.05, budget_factor=1, n_step_cap=8,
                  mode="loop", cap="reference", steps_per_pass=1, clip_to_occupancy=False):
-        import math
-        if mode not in ("loop", "fused"):
-            raise ValueError("mode must be 'loop' or 'fused', not %r" % (mode,))
-        if isinstance(steps_per_pass, bool) or steps_per_pass not in self.STEPS_PER_PASS:
-            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (steps_per_pass,))
+        super().__init__(density_bitfield, bound, cascade, grid_size, aabb, min_near, budget_factor, n_step_cap, mode, cap, chunk=4,
+                         clip_to_occupancy=clip_to_occupancy)
+        self.steps_per_pass = self._checked_steps_per_pass(steps_per_pass)
         if mode == "loop" and steps_per_pass != 1:
             raise ValueError("steps_per_pass is the fused mode's launch shape: mode 'loop' has its own schedule (budget_factor, n_step_cap)")
-        self.steps_per_pass = int(steps_per_pass)
         if mode == "loop" and clip_to_occupancy:
             raise ValueError("clip_to_occupancy belongs to mode 'fused': the loop's march kernels test every cell")
-        if cap not in ("reference", "per_ray"):
-            raise ValueError("cap must be 'reference' or 'per_ray', not %r" % (cap,))
         if mode == "fused" and cap == "reference" and int(n_step_cap) != 8:
             raise ValueError("mode 'fused' with cap 'reference' replays the schedule with the reference's step cap: n_step_cap must be 8")
-        self.mode, self.cap = mode, cap
         self.net = net
-        self.bound = float(bound)
-        self.cascade = cascade if cascade is not None else 1 + math.ceil(math.log2(bound))   # renderer.py:93
-        self.grid_size = grid_size
-        self.bitfield = density_bitfield.contiguous()
-        dev = self.bitfield.device
-        if aabb is None:
-            aabb = torch.tensor([-bound, -bound, -bound, bound, bound, bound], dtype=torch.float32, device=dev)
-        self.aabb = aabb.to(dev, torch.float32).contiguous()
-        self.min_near = float(min_near)
-        self.budget_factor, self.n_step_cap = int(budget_factor), int(n_step_cap)
-        self.chunk, self.lookahead = 4, 2
-        self._buf = None
-        self._fbuf = None
-        # fused mode, cap "reference", when this renderer draws a TILE of a frame: the frame's ray count (the N of renderer.py:513) and a
-        # callable that sums the [max_steps + 1] int32 histogram over the tiles in place (dist.ShardedFrame.configure sets both)
-        self.frame_rays_total = None
-        self.cap_exchange = None
-        # fused mode: confine every ray's march to the bounds of the occupied cells (lz_occupied_bounds): same samples, bit for bit
-        self.clip_to_occupancy = bool(clip_to_occupancy)
-        self.occupancy_margin = 8      # cells; see occupied_bounds()
-        self._occ = None
 
-    # the cached box of the occupied cells: TriplaneRenderer's rule (tensor identity plus version) on this renderer's bitfield
-    occupied_bounds = TriplaneRenderer.occupied_bounds
-    invalidate_occupancy = TriplaneRenderer.invalidate_occupancy
+    def _checked_steps_per_pass(self, spp):
+        if isinstance(spp, bool) or spp not in self.STEPS_PER_PASS:
+            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (spp,))
+        return int(spp)
 
-    def _buffers(self, N, dev):
-        rows = max(N * self.budget_factor, N)
-        b = self._buf
-        if b is None or b["N"] != N or b["rows"] != rows or b["dev"] != dev:
-            f = dict(dtype=torch.float32, device=dev)
-            i = dict(dtype=torch.int32, device=dev)
-            b = dict(N=N, rows=rows, dev=dev, nears=torch.empty(N, **f), fars=torch.empty(N, **f), rays_alive=[torch.empty(N, **i), torch.empty(N, **i)],
-                     rays_t=torch.empty(N, **f), weights_sum=torch.empty(N, **f), depth=torch.empty(N, **f), image=torch.empty(N, 3, **f),
-                     out=torch.empty(N, 3, **f), xyzs=torch.zeros(rows, 3, **f), dirs=torch.zeros(rows, 3, **f), deltas=torch.zeros(rows, 2, **f),
-                     feats=torch.zeros(rows, 32, dtype=self.net.table.dtype, device=dev), sigmas=torch.empty(rows, **f), rgbs=torch.empty(rows, 3, **f),
-                     state=torch.zeros(_STATE_INTS, **i), workspace=torch.empty(4096, **i), ray_counts=torch.zeros(N, **i),
-                     ring=[torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(4)])
-            self._buf = b
-        return b
+    @staticmethod
+    def _check_ray_count(N):
+        if N > MAX_RAYS_PER_PASS:
+            raise RuntimeError("HashgridRenderer renders at most %d rays per call" % MAX_RAYS_PER_PASS)
+
+    def _loop_extras(self, N, rows, dev):
+        return dict(feats=torch.zeros(rows, 32, dtype=self.net.table.dtype, device=dev))
 
     @torch.no_grad()
     def render(self, rays_o, rays_d, dt_gamma=1.0 / 256, max_steps=128, T_thresh=1e-4, bg_color=1.0, count_samples=False, rgb24=False,
@@ -295,84 +263,26 @@ class HashgridRenderer:
         perturb: the reference's inference loop passes `perturb` to march_rays on its FIRST iteration only (renderer.py:344,521), where
         every ray's start moves by clamp(near * dt_gamma, dt_min, dt_max) * U[0,1) (raymarching.cu:873).  `noises` [N] supplies the draws
         (tests; default torch.rand like raymarching.py:298).  Both modes, the same bits."""
-        rays_o = rays_o.reshape(-1, 3).float().contiguous()
-        rays_d = rays_d.reshape(-1, 3).float().contiguous()
-        N, dev = rays_o.shape[0], rays_o.device
-        if perturb and noises is None:
-            noises = torch.rand(N, dtype=torch.float32, device=dev)
-        if noises is not None:
-            noises = noises.reshape(-1).to(dev, torch.float32).contiguous()
-            if noises.numel() != N:
-                raise RuntimeError("noises must hold one value per ray")
-        if N > MAX_RAYS_PER_PASS:
-            raise RuntimeError("HashgridRenderer renders at most %d rays per call" % MAX_RAYS_PER_PASS)
+        rays_o, rays_d, N, dev, noises = self._rays(rays_o, rays_d, perturb, noises)
+        self._check_ray_count(N)
         tile = self.mode == "fused" and self.cap == "reference" and self.frame_rays_total is not None
         if N == 0 and not tile:       # (an empty tile of a larger frame still takes part in the exchange of the histogram)
-            from .renderer import _empty_result
             return _empty_result(dev, count_samples, rgb24, ambient=False)
         if self.mode == "fused":
             return self._render_fused(rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24, noises)
         b = self._buffers(N, dev)
-        call("lz_near_far_from_aabb", ptr(rays_o), ptr(rays_d), ptr(self.aabb), N, self.min_near, ptr(b["nears"]), ptr(b["fars"]), stream())
-        if count_samples:
-            b["ray_counts"].zero_()
-        starts = b["nears"]
-        if noises is not None:    # the loop's first march starts every ray at its perturbed t (lz_loop_begin copies `starts` into rays_t)
-            starts = torch.empty_like(b["nears"])
-            call("lz_perturb_starts", ptr(b["nears"]), ptr(noises), float(dt_gamma), int(max_steps), int(self.cascade), int(self.grid_size), N, ptr(starts),
-                 stream())
-        call("lz_loop_begin", N, int(max_steps), N * self.budget_factor, self.n_step_cap, ptr(starts), ptr(b["rays_alive"][0]), ptr(b["rays_t"]),
-             ptr(b["weights_sum"]), ptr(b["depth"]), ptr(b["image"]), None, None, None, ptr(b["state"]), ptr(b["workspace"]), stream())
+        self._begin(b, rays_o, rays_d, N, dt_gamma, max_steps, count_samples, noises)
         net, e = self.net, self.net.encoder
-        f = _lib.FrameNgp()
-        p = lambda t: t.data_ptr()
-        f.packed, f.embeddings, f.offsets, f.feats = p(net.packed), p(net.table), p(net.offsets), p(b["feats"])
+        f = self._fill_loop(_lib.FrameNgp(), b, rays_o, rays_d, N, dt_gamma, max_steps, T_thresh, count_samples)
+        f.packed, f.embeddings, f.offsets, f.feats = net.packed.data_ptr(), net.table.data_ptr(), net.offsets.data_ptr(), b["feats"].data_ptr()
         f.enc_L, f.enc_H, f.enc_S, f.emb_f16 = e.num_levels, e.base_resolution, net.S, int(net.half_tables)
-        f.state, f.workspace = p(b["state"]), p(b["workspace"])
-        f.rays_alive[0], f.rays_alive[1] = p(b["rays_alive"][0]), p(b["rays_alive"][1])
-        f.rays_t, f.rays_o, f.rays_d, f.nears, f.fars, f.grid = p(b["rays_t"]), p(rays_o), p(rays_d), p(b["nears"]), p(b["fars"]), p(self.bitfield)
-        f.xyzs, f.dirs, f.deltas, f.sigmas, f.rgbs = p(b["xyzs"]), p(b["dirs"]), p(b["deltas"]), p(b["sigmas"]), p(b["rgbs"])
-        f.weights_sum, f.depth, f.image = p(b["weights_sum"]), p(b["depth"]), p(b["image"])
-        f.ray_counts = p(b["ray_counts"]) if count_samples else None
-        f.N, f.max_steps, f.C, f.H = N, int(max_steps), int(self.cascade), int(self.grid_size)
-        f.bound, f.dt_gamma, f.T_thresh = self.bound, float(dt_gamma), float(T_thresh)
-        f.sample_budget, f.n_step_cap = N * self.budget_factor, self.n_step_cap
-        limit = int(max_steps) + 1            # n_step >= 1; the state of iteration k is committed by iteration k + 1's launches
-        cur, it, pending = 0, 0, []
-        while it < limit:
-            n = min(self.chunk, limit - it)
-            if net.precision == "f16":
-                call("lz_ngp_loop_run_f16", C.byref(f), ptr(net.packed16), cur, n, stream())
-            else:
-                call("lz_ngp_loop_run", C.byref(f), cur, n, stream())
-            cur = (cur + n) & 1
-            it += n
-            k = len(pending)
-            slot = b["ring"][k % len(b["ring"])]
-            slot.copy_(b["state"][:8], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append((ev, slot))
-            if k >= self.lookahead:       # look at the chunk `lookahead` chunks back: the queue never drains, few no-op chunks are enqueued
-                ev_old, slot_old = pending[k - self.lookahead]
-                ev_old.synchronize()
-                if int(slot_old[3]) == 1:
-                    break
-        bg = bg_color.to(dev, torch.float32).expand(N, 3).contiguous() if torch.is_tensor(bg_color) else None
-        bg_scalar = 1.0 if bg is not None else float(bg_color)
-        if rgb24:
-            if b.get("out_rgb24") is None:
-                b["out_rgb24"] = torch.empty(N, 3, dtype=torch.uint8, device=dev)
-            call("lz_final_blend_rgb24", ptr(b["image"]), ptr(b["weights_sum"]), ptr(bg), bg_scalar, N, ptr(b["out"]), ptr(b["out_rgb24"]), stream())
+        if net.precision == "f16":
+            enqueue = lambda k, n: call("lz_ngp_loop_run_f16", C.byref(f), ptr(net.packed16), k & 1, n, stream())
         else:
-            call("lz_final_blend", ptr(b["image"]), ptr(b["weights_sum"]), ptr(bg), bg_scalar, N, ptr(b["out"]), stream())
-        self._keep = (bg, rays_o, rays_d, noises)
-        res = dict(image=b["out"], image_raw=b["image"], weights_sum=b["weights_sum"], depth=b["depth"], state=b["state"])
-        if count_samples:
-            res["ray_counts"] = b["ray_counts"]
-        if rgb24:
-            res["image_rgb24"] = b["out_rgb24"]
-        return res
+            enqueue = lambda k, n: call("lz_ngp_loop_run", C.byref(f), k & 1, n, stream())
+        # n_step >= 1: max_steps iterations suffice; the state of iteration k is committed by iteration k + 1's launches
+        self._poll(b, enqueue, int(max_steps) + 1, self.chunk, self.lookahead)
+        return self._finish(b, N, dev, bg_color, count_samples, rgb24, (rays_o, rays_d, noises))
 
     # ---- the whole frame as one persistent kernel (csrc/lz_ngp_frame.hip, csrc/lz_ngp_frame_spp.hip) ----
     @property
@@ -383,23 +293,8 @@ class HashgridRenderer:
             return None
         return int(self._fbuf["state"][13]) or 1      # LZNF_SPP: written by the S > 1 kernels, 0 after the S = 1 kernels
 
-    def _fused_buffers(self, N, dev):
-        b = self._fbuf
-        if b is None or b["N"] != N or b["dev"] != dev:
-            f = dict(dtype=torch.float32, device=dev)
-            i = dict(dtype=torch.int32, device=dev)
-            b = dict(N=N, dev=dev, nears=torch.empty(N, **f), fars=torch.empty(N, **f), rays_t=torch.empty(N, **f), order=torch.empty(N, **i),
-                     state=torch.zeros(1024, **i), keys=torch.empty(N, dtype=torch.uint8, device=dev), scratch=torch.empty(N, **f),
-                     weights_sum=torch.empty(N, **f), depth=torch.empty(N, **f), image=torch.empty(N, 3, **f), out=torch.empty(N, 3, **f),
-                     ray_counts=None, ray_last=torch.empty(N, **i), cap_ws=None, t_end=None, out_rgb24=None)
-            self._fbuf = b
-        return b
-
-    def _render_fused(self, rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24=False, noises=None):
-        ctx = self.fused_begin(rays_o, rays_d, dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24, noises)
-        if ctx["deferred"] and self.cap_exchange is not None:
-            self.cap_exchange(ctx["hist"])
-        return self.fused_finish(ctx)
+    def _fused_extras(self, N, dev):
+        return dict(scratch=torch.empty(N, dtype=torch.float32, device=dev))
 
     def fused_begin(self, rays_o, rays_d, dt_gamma=1.0 / 256, max_steps=128, T_thresh=1e-4, bg_color=1.0, count_samples=False, rgb24=False,
                     noises=None):
@@ -411,73 +306,30 @@ class HashgridRenderer:
         at.  With frame_rays_total unset (a whole frame) and for cap = "per_ray" everything happens in fused_begin."""
         if self.mode != "fused":
             raise RuntimeError("fused_begin / fused_finish belong to mode 'fused'")
-        spp = self.steps_per_pass
-        if isinstance(spp, bool) or spp not in self.STEPS_PER_PASS:
-            raise ValueError("steps_per_pass must be 0 (auto), 1, 2, 4, 8 or 16, not %r" % (spp,))
-        rays_o = rays_o.reshape(-1, 3).float().contiguous()
-        rays_d = rays_d.reshape(-1, 3).float().contiguous()
-        N, dev = rays_o.shape[0], rays_o.device
-        if N > MAX_RAYS_PER_PASS:
-            raise RuntimeError("HashgridRenderer renders at most %d rays per call" % MAX_RAYS_PER_PASS)
-        if noises is not None:
-            noises = noises.reshape(-1).to(dev, torch.float32).contiguous()
-            if noises.numel() != N:
-                raise RuntimeError("noises must hold one value per ray")
-        b = self._fused_buffers(N, dev)
-        net, e = self.net, self.net.encoder
-        if count_samples and b["ray_counts"] is None:
-            b["ray_counts"] = torch.zeros(N, dtype=torch.int32, device=dev)
-        bg = bg_color.to(dev, torch.float32).expand(N, 3).contiguous() if torch.is_tensor(bg_color) else None
-        f = _lib.FrameNgpFused()
+        self._checked_steps_per_pass(self.steps_per_pass)
+        self._check_ray_count(rays_o.reshape(-1, 3).shape[0])
+        return self._fused_begin(rays_o, rays_d, (), dt_gamma, max_steps, T_thresh, bg_color, count_samples, rgb24, noises)
+
+    def _cap_total(self, N, total):
+        # the ray budget of the schedule the loop runs (renderer.py:513 with budget_factor = 1), of the whole frame for a tile
+        return (N if total is None else total) * self.budget_factor, total is not None
+
+    def _fused_launch(self, ctx, opts, cond):
+        f, net, e = ctx["f"], self.net, self.net.encoder
         p = lambda t: None if t is None else t.data_ptr()
         f.precision = 1 if net.precision == "f16" else 0
         f.packed, f.packed16 = p(net.packed), p(net.packed16)
         f.embeddings, f.offsets, f.emb_f16 = p(net.table), p(net.offsets), int(net.half_tables)
         f.enc_L, f.enc_H, f.enc_S = e.num_levels, e.base_resolution, net.S
-        f.rays_o, f.rays_d, f.grid, f.aabb = p(rays_o), p(rays_d), p(self.bitfield), p(self.aabb)
-        for k in ("nears", "fars", "rays_t", "order", "state", "keys", "scratch", "weights_sum", "depth", "image", "out"):
-            setattr(f, k, p(b[k]))
-        f.bg, f.bg_scalar = p(bg), 1.0 if bg is not None else float(bg_color)
-        f.ray_counts = p(b["ray_counts"]) if count_samples else None
-        f.bound, f.dt_gamma, f.T_thresh, f.min_near = self.bound, float(dt_gamma), float(T_thresh), self.min_near
-        f.N, f.max_steps, f.C, f.H = N, int(max_steps), int(self.cascade), int(self.grid_size)
-        if self.cap == "reference":
-            need = 2 * int(max_steps) + 24            # LZ_FRAME_CAP_WS_INTS
-            if b["cap_ws"] is None or b["cap_ws"].numel() < need:
-                b["cap_ws"] = torch.zeros(need, dtype=torch.int32, device=dev)
-            f.cap_mode, f.ray_last, f.cap_ws = 1, p(b["ray_last"]), p(b["cap_ws"])
-            f.N_total = N * self.budget_factor        # the ray budget of the schedule the loop runs (renderer.py:513 with budget_factor = 1)
+        f.scratch = p(ctx["b"]["scratch"])
         # the options next to the frame: none in use -> no record, and the call is lz_ngp_frame_render_spp launch for launch
-        o, deferred = _lib.FrameNgpFusedOpts(), False
-        if noises is not None:
-            o.noises = p(noises)
-        if self.clip_to_occupancy:
-            if b["t_end"] is None:
-                b["t_end"] = torch.empty(N, dtype=torch.float32, device=dev)
-            o.occupied_aabb, o.t_end = p(self.occupied_bounds()), p(b["t_end"])
-        if rgb24:
-            if b["out_rgb24"] is None:
-                b["out_rgb24"] = torch.empty(N, 3, dtype=torch.uint8, device=dev)
-            o.out_rgb24 = p(b["out_rgb24"])
-        if self.cap == "reference" and self.frame_rays_total is not None:
-            if int(self.frame_rays_total) < N:
-                raise ValueError("frame_rays_total is the ray count of the whole frame (>= the rays of this call)")
-            f.N_total, o.defer_finish = int(self.frame_rays_total) * self.budget_factor, 1
-            deferred = True
-        used = noises is not None or self.clip_to_occupancy or rgb24 or deferred
-        call("lz_ngp_frame_render_opts", C.byref(f), C.byref(o) if used else None, int(spp), None, stream())
-        keep = (bg, rays_o, rays_d, noises)
-        self._keep = keep
-        return dict(f=f, o=o if used else None, spp=int(spp), b=b, keep=keep, deferred=deferred, count_samples=count_samples, rgb24=rgb24,
-                    hist=b["cap_ws"][: int(max_steps) + 1] if deferred else None)
+        o = None
+        if opts:
+            o = _lib.FrameNgpFusedOpts()
+            for k, v in opts.items():
+                setattr(o, k, v)
+        ctx.update(o=o, spp=int(self.steps_per_pass))
+        call("lz_ngp_frame_render_opts", C.byref(f), None if o is None else C.byref(o), ctx["spp"], None, stream())
 
-    def fused_finish(self, ctx):
-        b = ctx["b"]
-        if ctx["deferred"]:
-            call("lz_ngp_frame_finish", C.byref(ctx["f"]), C.byref(ctx["o"]), ctx["spp"], stream())
-        res = dict(image=b["out"], image_raw=b["image"], weights_sum=b["weights_sum"], depth=b["depth"], state=b["state"])
-        if ctx["count_samples"]:
-            res["ray_counts"] = b["ray_counts"]
-        if ctx["rgb24"]:
-            res["image_rgb24"] = b["out_rgb24"]
-        return res
+    def _fused_finish_launch(self, ctx):
+        call("lz_ngp_frame_finish", C.byref(ctx["f"]), C.byref(ctx["o"]), ctx["spp"], stream())
