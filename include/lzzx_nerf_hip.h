@@ -383,6 +383,29 @@ int lz_density_grid_points(const float* noise, uint32_t C, uint32_t G, float bou
 int lz_density_grid_update(const float* sigmas, float density_scale, float decay, float density_thresh, uint32_t C, uint32_t G,
                            float* density_grid, uint8_t* bitfield, float* stats, void* workspace, lz_stream_t stream);
 
+/* NeRFNetwork.density (nerf_triplane/network.py:283-311): the fused head cut off behind sigma_net -- no SH, no colour net, no
+ * uncertainty (additive under ABI 11; csrc/lz_density.hip).  xyzs [M,3] -> sigma [M], amb_aud [M], amb_eye [M] (may be NULL; left
+ * untouched without an eye input as by lz_triplane_head_forward) with the bits lz_triplane_head_forward writes for the same rows, and
+ * geo_feat [M,64] (may be NULL: sigma_net.2's 64 geo rows are then not evaluated) -- f32 for p->precision 0 / 2, half for precision 1
+ * (the reference's autocast density() returns a half geo_feat).  p->packed is the forward's (lz_head_pack_weights /
+ * lz_head_pack_weights_f16w); p->ind_code and p->testing are not looked at.  `count` as in lz_triplane_head_forward. */
+int lz_triplane_head_density(const lz_head_params* p, const float* xyzs, uint32_t M, const int32_t* count, float* sigma, float* amb_aud,
+                             float* amb_eye, void* geo_feat, lz_stream_t stream);
+/* The same query on a lattice of points made in the kernel, storing only the outputs asked for (sigma, amb_aud, amb_eye: each may be
+ * NULL, not all three).  Two point sources:
+ *   LZ_LATTICE_CELLS  the occupancy grid's cells -- update_extra_state (renderer.py:739-751), get_audio_grid / get_eye_grid
+ *     (renderer.py:823-933): row n of C * G^3 is cascade n / G^3, cell in meshgrid order (x slowest, z fastest), its point formed from
+ *     noise [C, G^3, 3] by the rule of lz_density_grid_points with bound = p->bound; sigma is what lz_density_grid_update consumes.
+ *     X, Y, Z are not looked at.
+ *   LZ_LATTICE_AXES   extract_fields (nerf_triplane/utils.py:348-363): row (i * Ry + j) * Rz + k is the point (X[i], Y[j], Z[k]) of
+ *     three device arrays X [Rx], Y [Ry], Z [Rz] (the caller's torch.linspace); noise, C, G are not looked at.
+ * C * G == 0 (cells) and Rx * Ry * Rz == 0 (axes) return LZ_OK before anything else; the row count must be < 2^32. */
+#define LZ_LATTICE_CELLS 0u
+#define LZ_LATTICE_AXES 1u
+int lz_triplane_density_lattice(const lz_head_params* p, uint32_t source, const float* noise, uint32_t C, uint32_t G, const float* X,
+                                uint32_t Rx, const float* Y, uint32_t Ry, const float* Z, uint32_t Rz, float* sigma, float* amb_aud,
+                                float* amb_eye, lz_stream_t stream);
+
 /* mark_untrained_grid (renderer.py:633-695): density_grid[cas, morton(cell)] = -1 for every cell none of the B cameras
  * (poses [B,4,4] c2w, device) sees; count (optional, int32 [C, G^3], Morton-ordered) = cameras covering each cell. */
 int lz_mark_untrained_grid(const float* poses, uint32_t B, float fx, float fy, float cx, float cy, uint32_t C, uint32_t G,

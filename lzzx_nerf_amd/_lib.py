@@ -197,6 +197,9 @@ SIGNATURES = {
     "lz_density_grid_torso_points": [vp, u32, vp, vp],
     "lz_density_grid_torso_update": [vp, f32, f32, u32, vp, vp, vp, vp],
     "lz_density_grid_update": [vp, f32, f32, f32, u32, u32, vp, vp, vp, vp, vp],
+    # NeRFNetwork.density: the head cut off behind sigma_net (csrc/lz_density.hip, head.py: density, occupancy.py)
+    "lz_triplane_head_density": [C.POINTER(HeadParams), vp, u32, vp, vp, vp, vp, vp, vp],
+    "lz_triplane_density_lattice": [C.POINTER(HeadParams), u32, vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp],
     "lz_linear_forward": [vp, u32, vp, vp, u32, vp, u32, u32, u32, u32, i32, vp],
     "lz_linear_grad_w": [vp, u32, vp, vp, u32, vp, u32, u32, u32, u32, vp],
     "lz_triplane_head_forward_record": [C.POINTER(HeadParams), vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, vp],
@@ -222,6 +225,7 @@ SIGNATURES = {
 }
 LZ_OBJECTIVE_WS_BYTES = 64 + 2048 * 8 * 8   # include/lzzx_nerf_hip.h
 LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
+LZ_LATTICE_CELLS, LZ_LATTICE_AXES = 0, 1
 PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_device_ok": ([], i32), "lz_train_group_size": ([], i32),
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),

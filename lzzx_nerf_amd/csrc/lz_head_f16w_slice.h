@@ -61,6 +61,15 @@ __device__ __forceinline__ void w_layer(const lz_h8* __restrict__ wl, int lane, 
 #pragma unroll
         for (int ft = 0; ft < NT; ft++) acc[ft] = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag[(ks * NT + ft) * 64], b[ks], acc[ft], 0, 0, 0);
 }
+// output tile FT of a layer alone: its accumulators see the MFMAs w_layer gives them, in the same k order
+template <int LAYER, int FT>
+__device__ __forceinline__ void w_layer_tile(const lz_h8* __restrict__ wl, int lane, const lz_h8 (&b)[W_KS[LAYER]], lz_f16v& acc) {
+    constexpr int KS = W_KS[LAYER], NT = W_NT[LAYER];
+    static_assert(0 <= FT && FT < NT, "tile of the layer");
+    const lz_h8* frag = wl + w_frag_base(LAYER) * 64 + lane;
+#pragma unroll
+    for (int ks = 0; ks < KS; ks++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag[(ks * NT + FT) * 64], b[ks], acc, 0, 0, 0);
+}
 
 // registers 8 u .. 8 u + 7 of a D tile -> the B operand of k-step 2 t + u of the next layer (half output of an autocast Linear [+ relu])
 __device__ __forceinline__ lz_h8 w_pack(const lz_f16v& d, int u, bool relu) {
@@ -119,8 +128,13 @@ __device__ __forceinline__ void lz_head16w_stage(const LzHead16Args& P, lz_h8* w
 #ifndef LZ_F16W_PRIO
 #define LZ_F16W_PRIO 1   // the frame kernel runs march + gather addresses at a raised wave priority and drops it once a gather call has issued its loads (same-box A/B, three alternations: 1.789 -> 1.783, 1.800 -> 1.791 ms, cfg5 0.770 -> 0.762; -DLZ_F16W_PRIO=0 switches it off)
 #endif
-template <bool IN_RANGE = false, bool YIELD = false, typename ShFn>   // SH(4) source: LzShFromDir (lz_head_slice.h) or the frame kernel's per-ray LDS copy
-__device__ __forceinline__ void lz_head16w_slice(const LzHead16Ctx& hc, int lane, float px, float py, float pz, ShFn shfn, LzHead16wOut& out) {
+// CUT (lz_head_slice.h: LZ_CUT_*): NeRFNetwork.density under autocast, the slice cut off behind sigma_net.2.  LZ_CUT_DENSITY runs only the
+// tile of sigma_net.2 that holds the sigma row; LZ_CUT_DENSITY_GEO runs all three and hands this lane's 32 geo_feat halves to `geo_out`
+// ([2 t + u][j] = feature 32 t + 16 u + 8 (j >> 2) + 4 h + (j & 3)).  out.b = sigma on lanes h == 1 (chain B's exp2 on the same product),
+// out.ambaud and out.eyeatt as in the full slice; out.a and out.unc are not written.
+template <bool IN_RANGE = false, bool YIELD = false, int CUT = LZ_CUT_NONE, typename ShFn>   // SH(4) source: LzShFromDir (lz_head_slice.h) or the frame kernel's per-ray LDS copy
+__device__ __forceinline__ void lz_head16w_slice(const LzHead16Ctx& hc, int lane, float px, float py, float pz, ShFn shfn, LzHead16wOut& out,
+                                                 lz_h8* geo_out = nullptr) {
     const int h = lane >> 5;
     // ---------------- gather (f32, lz_head_gather.h, the f32 kernels' arithmetic): 18 features of this lane's sample, 2 x 36 loads ----------------
     lz_h8 bx[3];
@@ -183,13 +197,28 @@ __device__ __forceinline__ void lz_head16w_slice(const LzHead16Ctx& hc, int lane
         lz_f16v s2[2] = {w_zero(), w_zero()};
         w_layer<W_S2>(hc.wl, lane, b2, s2);
         const lz_h8 b3[4] = {w_pack(s2[0], 0, true), w_pack(s2[0], 1, true), w_pack(s2[1], 0, true), w_pack(s2[1], 1, true)};
-        lz_f16v s3[3] = {w_zero(), w_zero(), w_zero()};
-        w_layer<W_S3>(hc.wl, lane, b3, s3);
-        geo16[0] = w_pack(s3[0], 0, false);   // geo_feat, no activation (network.py:304)
-        geo16[1] = w_pack(s3[0], 1, false);
-        geo16[2] = w_pack(s3[1], 0, false);
-        geo16[3] = w_pack(s3[1], 1, false);
-        spre = (float)(_Float16)s3[2][0];      // the sigma row (half): row 4 of the third tile = register 0 of lanes h == 1
+        if constexpr (CUT == LZ_CUT_DENSITY) {
+            lz_f16v sg = w_zero();
+            w_layer_tile<W_S3, 2>(hc.wl, lane, b3, sg);
+            spre = (float)(_Float16)sg[0];
+        } else {
+            lz_f16v s3[3] = {w_zero(), w_zero(), w_zero()};
+            w_layer<W_S3>(hc.wl, lane, b3, s3);
+            geo16[0] = w_pack(s3[0], 0, false);   // geo_feat, no activation (network.py:304)
+            geo16[1] = w_pack(s3[0], 1, false);
+            geo16[2] = w_pack(s3[1], 0, false);
+            geo16[3] = w_pack(s3[1], 1, false);
+            spre = (float)(_Float16)s3[2][0];      // the sigma row (half): row 4 of the third tile = register 0 of lanes h == 1
+        }
+    }
+    if constexpr (CUT != LZ_CUT_NONE) {   // density(): nothing below is reached
+        out.b = __builtin_amdgcn_exp2f(spre * 1.44269504088896340736f);   // chain B on h == 1
+        out.eyeatt = eyeatt;
+        if constexpr (CUT == LZ_CUT_DENSITY_GEO) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) geo_out[k] = geo16[k];
+        }
+        return;
     }
     // ---------------- colour net: [SH 16 | geo 64 | ind 4] -> 64 -> 3 ----------------
     {

@@ -2,6 +2,7 @@
 // head kernel (lz_head.hip: lz_k_triplane_head) and the fused frame kernel (lz_frame.hip: lz_k_frame), so that both evaluate
 // NeRFNetwork.forward (nerf_triplane/network.py:252-311) with the same instruction sequence, bit for bit.  Lane (s = lane & 15,
 // q = lane >> 4) owns sample s and a quarter of its features; see lz_head.hip for the layer chaining and the summation orders.
+// NeRFNetwork.density (lz_density.hip) is the same function cut off behind sigma_net by a compile-time switch (CUT, below).
 #ifndef LZ_HEAD_SLICE_H
 #define LZ_HEAD_SLICE_H
 #include "lz_common.h"
@@ -166,9 +167,24 @@ __device__ __forceinline__ void lz_slice_relu_fence() {
 // W_c0[:, geo] (Wg s2) = (W_c0[:, geo] Wg) s2: the host packs the 64 x 64 product into colour_net.0's geo columns (head.py: fold_geo) and
 // the slice hands s2 to the colour net directly -- 64 of the 361 MFMAs per slice are never issued.  sigma (the VALU row of sigma_net.2 on
 // s2) is unchanged bit for bit; rgb moves by the reassociation, a few 1e-7.
-template <bool TRAIN_UNC, bool FOLD = false, bool IN_RANGE = false, bool YIELD = false, typename ShFn>
-__device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, float px, float py, float pz, ShFn shfn, LzHeadOut& out) {
+// CUT: NeRFNetwork.density (network.py:283-311), the slice cut off behind sigma_net (lz_density.hip).  LZ_CUT_DENSITY stops at the sigma
+// row: no geo rows of sigma_net.2, no SH, no colour net, no uncertainty constant; out.sigma / ambaud / eyeatt are the full slice's bits
+// (the same fragments in the same k order; sigma = lz_expf on the same argument).  LZ_CUT_DENSITY_GEO also runs the geo rows and hands
+// this lane's 16 geo_feat values (feature 16 ft + 4 q + r at [4 ft + r]) to `geo_out`.  out.rgb / out.unc are not written.
+enum { LZ_CUT_NONE = 0, LZ_CUT_DENSITY = 1, LZ_CUT_DENSITY_GEO = 2 };
+// the SH source of a cut slice: nothing asks it for a value
+struct LzShNone {
+    static constexpr bool C1_PARTIAL = false;
+    __device__ __forceinline__ void issue(int) {}
+    __device__ __forceinline__ void prepare() {}
+    __device__ __forceinline__ float comp_iq(int, int) const { return 0.0f; }
+    __device__ __forceinline__ float comp_qj(int, int) const { return 0.0f; }
+};
+template <bool TRAIN_UNC, bool FOLD = false, bool IN_RANGE = false, bool YIELD = false, int CUT = LZ_CUT_NONE, typename ShFn>
+__device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, float px, float py, float pz, ShFn shfn, LzHeadOut& out,
+                                              float* geo_out = nullptr) {
     static_assert(!(TRAIN_UNC && FOLD), "the folded colour net is an inference arrangement");
+    static_assert(CUT == LZ_CUT_NONE || !(TRAIN_UNC || FOLD), "a density query has neither an uncertainty net nor a colour net to fold into");
     constexpr int WV = LzHeadLds<TRAIN_UNC>::WV;
     const int q = lane >> 4;
     // ---------------- gather: enc_x features f = 4i + q of sample s -> B operands (lz_head_gather.h) ----------------
@@ -254,7 +270,7 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
         lz_slice_relu_fence();
 #pragma unroll
         for (int j = 0; j < LZ_T; j++) uncv[j] = lz_softplusf(lz_lane_dot<2>(hc.wl + WV + LZ_WV_U2, q, bu[j]));
-    } else {
+    } else if constexpr (CUT == LZ_CUT_NONE) {
 #pragma unroll
         for (int j = 0; j < LZ_T; j++) uncv[j] = lz_softplusf(0.0f);   // network.py:243-249, 278
     }
@@ -323,7 +339,9 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
 #pragma unroll
                 for (int r = 0; r < 4; r++) b3[j][4 * ft + r] = lz_slice_relu(acc2[ft][j][r]);
         lz_slice_relu_fence();
-        if constexpr (FOLD) {
+        if constexpr (CUT == LZ_CUT_DENSITY) {
+            // density without geo_feat: the 64 geo MFMAs are never issued
+        } else if constexpr (FOLD) {
 #pragma unroll
             for (int j = 0; j < LZ_T; j++)
 #pragma unroll
@@ -344,6 +362,16 @@ __device__ __forceinline__ void lz_head_slice(const LzHeadCtx& hc, int lane, flo
         }
 #pragma unroll
         for (int j = 0; j < LZ_T; j++) sig_pre[j] = lz_lane_dot<4>(hc.wl + WV + LZ_WV_SIG, q, b3[j]);     // row 0 of sigma_net.2 on the VALU
+    }
+    if constexpr (CUT != LZ_CUT_NONE) {   // density(): sigma = exp(h0) (network.py:302) on every lane of the sample; nothing below is reached
+        out.sigma = lz_expf(sig_pre[0]);
+        out.ambaud = ambaud[0];
+        out.eyeatt = eyeatt[0];
+        if constexpr (CUT == LZ_CUT_DENSITY_GEO) {
+#pragma unroll
+            for (int k = 0; k < 16; k++) geo_out[k] = geo[0][k];
+        }
+        return;
     }
     // ---------------- colour net: [SH 16 | geo 64 | ind 4] -> 64 -> 3 ----------------
     float rgb[LZ_T][3];

@@ -16,6 +16,7 @@
 //     costs one device->host sync per iteration: 38 % of its loop time).
 //   * all kernels launch on the caller's stream.
 #include "lz_composite_train.h"
+#include "lz_density_cell.h"
 
 // ------------------------------------------------------------------------------------------------
 // ray generation (nerf_triplane/utils.py:226-312): B poses x N pixels.  `inds` (pixel = row * W + col, shared by the batch like the
@@ -206,23 +207,12 @@ extern "C" int lz_morton3D_dilation(const float* grid, uint32_t C, uint32_t H, f
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 lz_k_density_points(const float* __restrict__ noise, uint32_t C, uint32_t G, float bound, float* __restrict__ xyzs) {
-    const uint32_t G3 = G * G * G;
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= C * G3) return;
-    const uint32_t cas = n / G3, p = n - cas * G3;
-    // custom_meshgrid(xs, ys, zs) flattened: x slowest, z fastest (renderer.py:739-741)
-    const uint32_t c[3] = {p / (G * G), (p / G) % G, p % G};
-    // python doubles, then narrowed where torch multiplies an f32 tensor by a python scalar (renderer.py:747-751)
-    const double bc = fmin((double)(1u << cas), (double)bound);
-    const double half = bc / (double)G;
-    const float scale = (float)(bc - half), hgs = (float)half;
+    if (n >= C * G * G * G) return;
+    float xyz[3];
+    lz_density_cell_point(noise, n, G, bound, xyz);   // lz_density_cell.h
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
-        float v = (2.0f * (float)c[d]) / (float)(G - 1) - 1.0f;     // 2 * coords.float() / (grid_size - 1) - 1
-        v = v * scale;                                              // xyzs * (bound - half_grid_size)
-        const float nz = (noise[(size_t)n * 3 + d] * 2.0f - 1.0f) * hgs;   // (rand * 2 - 1) * half_grid_size
-        xyzs[(size_t)n * 3 + d] = v + nz;
-    }
+    for (int d = 0; d < 3; d++) xyzs[(size_t)n * 3 + d] = xyz[d];
 }
 
 extern "C" int lz_density_grid_points(const float* noise, uint32_t C, uint32_t G, float bound, float* xyzs, lz_stream_t stream) {

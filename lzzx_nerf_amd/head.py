@@ -125,3 +125,52 @@ class FusedTriplaneHead:
         return sig, rgb, aa, ae, un
 
     __call__ = forward
+
+    def _density_inputs(self, enc_a, eye):
+        enc_a = enc_a.reshape(-1).float().contiguous()
+        if enc_a.numel() != 32:
+            raise RuntimeError("enc_a must hold 32 audio features")
+        eye = None if eye is None else eye.reshape(-1).float().contiguous()
+        self._keep = (enc_a, None, eye)   # alive until the launch is enqueued (same stream -> ordering is enough)
+        return self._params(enc_a, None, eye, True), eye is not None and self.has_eye
+
+    def density(self, x, enc_a, eye=None, geo_feat=False, count_ptr=None, out=None):
+        """NeRFNetwork.density(x, enc_a, e) (network.py:283-311) as one launch that stops behind sigma_net (csrc/lz_density.hip): no SH, no
+        colour net.  x: [M, 3] f32 cuda.  Returns the reference's keys: sigma [M], ambient_aud [M,1], ambient_eye [M,1] (None without an
+        eye input) -- the bits forward() gives for the same points -- and, when asked for, geo_feat [M,64] (f32; half on the f16 head, as
+        under autocast).  `out`: a dict of preallocated tensors under the same keys (at least M rows each)."""
+        M = x.shape[0]
+        p, with_eye = self._density_inputs(enc_a, eye)
+        kw = dict(dtype=torch.float32, device=x.device)
+        o = dict(out) if out is not None else {}
+        o.setdefault("sigma", torch.empty(M, **kw))
+        o.setdefault("ambient_aud", torch.empty(M, 1, **kw))
+        if with_eye:
+            o.setdefault("ambient_eye", torch.empty(M, 1, **kw))
+        else:
+            o["ambient_eye"] = None
+        if geo_feat:
+            o.setdefault("geo_feat", torch.empty(M, 64, dtype=torch.float16 if self.precision == "f16" else torch.float32, device=x.device))
+        call("lz_triplane_head_density", C.byref(p), ptr(x), M, C.c_void_p(count_ptr) if count_ptr else None, ptr(o["sigma"]),
+             ptr(o["ambient_aud"]), ptr(o["ambient_eye"]), ptr(o["geo_feat"]) if geo_feat else None, stream())
+        return o
+
+    def density_lattice(self, enc_a, eye=None, noise=None, grid_size=0, axes=None, sigma=False, ambient=False):
+        """density() on points made in the kernel (lz_triplane_density_lattice), storing only what is asked for.  Either `noise`
+        [cascade, G^3, 3] with `grid_size` G -- the occupancy grid's cells, rows in the order lz_density_grid_update consumes -- or
+        `axes` = (X, Y, Z), three 1-d f32 cuda tensors: row (i Ry + j) Rz + k is (X[i], Y[j], Z[k]).  Returns (sigma, ambient_aud,
+        ambient_eye), flat [rows] f32; None where not asked for (ambient_eye also without an eye input)."""
+        p, with_eye = self._density_inputs(enc_a, eye)
+        if axes is None:
+            rows = noise.shape[0] * grid_size ** 3
+            src = (_lib.LZ_LATTICE_CELLS, ptr(noise), noise.shape[0], grid_size, None, 0, None, 0, None, 0)
+            dev = noise.device
+        else:
+            X, Y, Z = axes
+            rows = X.numel() * Y.numel() * Z.numel()
+            src = (_lib.LZ_LATTICE_AXES, None, 0, 0, ptr(X), X.numel(), ptr(Y), Y.numel(), ptr(Z), Z.numel())
+            dev = X.device
+        new = lambda want: torch.empty(rows, dtype=torch.float32, device=dev) if want else None
+        sig, aud, eyo = new(sigma), new(ambient), new(ambient and with_eye)
+        call("lz_triplane_density_lattice", C.byref(p), *src, ptr(sig), ptr(aud), ptr(eyo), stream())
+        return sig, aud, eyo
