@@ -406,6 +406,24 @@ int lz_triplane_density_lattice(const lz_head_params* p, uint32_t source, const 
                                 uint32_t Rx, const float* Y, uint32_t Ry, const float* Z, uint32_t Rz, float* sigma, float* amb_aud,
                                 float* amb_eye, lz_stream_t stream);
 
+/* extract_geometry's mcubes.marching_cubes(u, threshold) (nerf_triplane/utils.py:366-378) on the device (additive under ABI 11;
+ * csrc/lz_mesh.hip): u [Rx, Ry, Rz] f32 contiguous -- the lattice lz_triplane_density_lattice writes -- and thr give
+ * vertices [V, 3] f32 in INDEX coordinates (mcubes' convention; the affine of utils.py:377 is the caller's) and triangles [T, 3] int32.
+ * The mesh is a function of (u, thr) alone, the same bits on every call: solid(v) = v >= thr; vertex ids are the ranks of the keys
+ * 3 n + a of the cut lattice edges (node n = (i Ry + j) Rz + k, axis a); triangles are ordered by cell, then by the generated case table
+ * (include/lzzx_mc_tables.h), normals from solid to empty.
+ *   lz_mc_workspace  bytes of device workspace for a lattice (0 for an empty or an oversize one); 16-byte aligned, no initialisation.
+ *   lz_mc_count      first pass and scan: fills the workspace and writes totals[0] = V, totals[1] = T (device, uint32[2]).
+ *   lz_mc_emit       second pass, on the same u, thr and the workspace lz_mc_count filled: writes the first min(V, V_cap) vertices and
+ *                    the first min(T, T_cap) triangles, never a row at or behind the capacities (vertices / triangles may be NULL where
+ *                    its capacity is 0).
+ * (utils.py:366-378) A lattice with an extent below 2 has no cells: both entries return LZ_OK before anything else, launch nothing and
+ * leave totals untouched.  3 Rx Ry Rz >= 2^31 and null tensors are LZ_ERR_BAD_ARGUMENT before any launch. */
+size_t lz_mc_workspace(uint32_t Rx, uint32_t Ry, uint32_t Rz);
+int lz_mc_count(const float* u, uint32_t Rx, uint32_t Ry, uint32_t Rz, float thr, void* workspace, uint32_t* totals, lz_stream_t stream);
+int lz_mc_emit(const float* u, uint32_t Rx, uint32_t Ry, uint32_t Rz, float thr, const void* workspace, uint32_t V_cap, uint32_t T_cap,
+               float* vertices, int32_t* triangles, lz_stream_t stream);
+
 /* mark_untrained_grid (renderer.py:633-695): density_grid[cas, morton(cell)] = -1 for every cell none of the B cameras
  * (poses [B,4,4] c2w, device) sees; count (optional, int32 [C, G^3], Morton-ordered) = cameras covering each cell. */
 int lz_mark_untrained_grid(const float* poses, uint32_t B, float fx, float fy, float cx, float cy, uint32_t C, uint32_t G,

@@ -200,6 +200,9 @@ SIGNATURES = {
     # NeRFNetwork.density: the head cut off behind sigma_net (csrc/lz_density.hip, head.py: density, occupancy.py)
     "lz_triplane_head_density": [C.POINTER(HeadParams), vp, u32, vp, vp, vp, vp, vp, vp],
     "lz_triplane_density_lattice": [C.POINTER(HeadParams), u32, vp, u32, u32, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp],
+    # marching cubes on that lattice (csrc/lz_mesh.hip, lzzx_nerf_amd/mesh.py)
+    "lz_mc_count": [vp, u32, u32, u32, f32, vp, vp, vp],
+    "lz_mc_emit": [vp, u32, u32, u32, f32, vp, u32, u32, vp, vp, vp],
     "lz_linear_forward": [vp, u32, vp, vp, u32, vp, u32, u32, u32, u32, i32, vp],
     "lz_linear_grad_w": [vp, u32, vp, vp, u32, vp, u32, u32, u32, u32, vp],
     "lz_triplane_head_forward_record": [C.POINTER(HeadParams), vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, i32, vp],
@@ -230,7 +233,7 @@ PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_dev
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
          "lz_audio_train_workspace": ([], C.c_size_t), "lz_audio_track_workspace": ([u32, u32, u32], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
-         "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t)}
+         "lz_mc_workspace": ([u32, u32, u32], C.c_size_t), "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

@@ -125,6 +125,23 @@ class TalkingHeadFrame:
         return out
 
     @torch.no_grad()
+    def save_mesh(self, path, auds_or_enc_a, eye=None, resolution=256, threshold=10):
+        """`Trainer.save_mesh` (TrainerUtil.py:444-463) on the pipeline object: the head's density at `resolution`^3 nodes of the renderer's
+        aabb (the reference's aabb_infer), cut at `threshold` by marching cubes on the device, written to `path` as a PLY
+        (lzzx_nerf_amd/mesh.py).  auds_or_enc_a: the frame's audio windows [n_win, dim_in, 16] or an audio code [1, dim_aud] that
+        `render` returned; the smooth_lips state is neither used nor changed.  Returns (vertices, triangles) on the device."""
+        import os
+        from .mesh import extract_geometry, save_mesh
+        a = torch.as_tensor(auds_or_enc_a).to(self.audio.device, torch.float32)
+        enc_a = self.audio(a) if a.dim() == 3 else a
+        aabb = self.renderer.aabb
+        vertices, triangles = extract_geometry(self.head, enc_a, eye, aabb[:3], aabb[3:], resolution, threshold)
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        save_mesh(path, vertices, triangles)
+        return vertices, triangles
+
+    @torch.no_grad()
     def render_clip(self, poses, intrinsics, H, W, features, att_mode, first_index=0, eyes=None, ind_code=None, ind_code_torso=None,
                     bg_coords=None, bg_color=1.0, density_grid_torso=None, density_thresh_torso=None, **render_kw):
         """A clip of K = len(poses) frames from one audio track: a generator of one dict per frame, the dict `render` returns for that

@@ -12,6 +12,7 @@ never materialised for pixels that were not selected.
 import torch
 
 from ._util import call, ptr, stream
+from .mesh import extract_geometry   # noqa: F401 -- utils.py:366-378, next to get_rays as in the reference's module (on the fused head: mesh.py)
 
 
 def select_pixels(H, W, N=-1, patch_size=1, rect=None, device="cuda"):
