@@ -1128,6 +1128,49 @@ int lz_objective_jitter_forward(const float* raw_unc, const float* raw_aud, cons
 int lz_objective_jitter_backward(const float* grad_loss, const float* raw_unc, const float* raw_aud, const float* raw_eye, const float* reg_unc,
                                  const float* reg_aud, const float* reg_eye, uint32_t M, uint32_t flags, float scale, float* g_reg_unc,
                                  float* g_reg_aud, float* g_reg_eye, lz_stream_t stream);
+/* The gradient of pred = clamp(image_raw + (1 - weights_sum) bg, 0, 1) [N,3] back to its inputs, for a loss term that reads pred (the
+ * LPIPS terms below): g_image_raw [N,3] = g_pred where 0 <= image_raw + (1 - weights_sum) bg <= 1 (torch's clamp backward) and 0
+ * elsewhere, g_weights_sum [N] = -sum_c g_image_raw[c] bg[c].  bg / bg_mode / bg_scalar as in lz_objective_head_forward.  One elementwise
+ * launch.  Additive under ABI version 11. */
+int lz_objective_pred_backward(const float* g_pred, const float* image_raw, const float* weights_sum, const float* bg, uint32_t bg_mode,
+                               float bg_scalar, uint32_t N, float* g_image_raw, float* g_weights_sum, lz_stream_t stream);
+
+/* ---- Perceptual loss (csrc/lz_lpips.hip, lzzx_nerf_amd/perceptual.py) ----------------------------------------------
+ * Additive under ABI version 11: new entries only.  Together they replace lpips.LPIPS(net='alex').forward as called at
+ * nerf_triplane/TrainerUtil.py:283,309: LPIPS v0.1 on the AlexNet trunk in f32, value [P] and its gradient with respect to the first
+ * image.  Images are [P,3,H,W] f32 in [-1, 1], P >= 1, 31 <= H, W <= 256 (below 31 the second max-pool has no output); anything else is
+ * LZ_ERR_UNSUPPORTED, a null or misaligned tensor LZ_ERR_BAD_ARGUMENT, both before any launch.  P = 0 launches nothing.  No float
+ * atomics: same inputs, same bits; both images go through the trunk as rows of the same launches, so equal images give exactly 0. */
+typedef struct lz_lpips_weights {      /* HOST pointers, f32, the layouts of lpips.LPIPS(net='alex').state_dict() */
+    const float* conv_w[5];            /* [64,3,11,11] [192,64,5,5] [384,192,3,3] [256,384,3,3] [256,256,3,3] */
+    const float* conv_b[5];            /* [64] [192] [384] [256] [256] */
+    const float* lin_w[5];             /* the 1x1 lin layers, [64] [192] [384] [256] [256], non-negative */
+    float shift[3], scale[3];          /* the scaling layer: x -> (x - shift) / scale */
+} lz_lpips_weights;
+/* replaces the weights held by lpips.LPIPS(net='alex') (TrainerUtil.py:283,309): floats of the packed image */
+size_t lz_lpips_packed_floats(void);
+/* replaces the construction of lpips.LPIPS(net='alex') (TrainerUtil.py:283,309).  HOST code, no launch: writes the packed image into
+ * `packed` (host memory, packed_floats >= lz_lpips_packed_floats()), which the caller copies to 16-byte aligned device memory once.
+ * Layout, in floats: shift[3], 0, scale[3], 0 | per layer l = 0..4 the forward pack and the bias [Cout] | the transposed packs of layers
+ * 1..4 | conv1's gather pack [ky*11+kx][co][4] (W[co][ci][ky][kx] at [..][ci], 0 at [..][3]) | lin[0..4].  A pack of a convolution seen as
+ * n outputs x T taps x C channels is [n/16][ceil(T C / 16)][64 lanes][4]: element (t, jj, lane, c) holds output n = 16 t + (lane & 15) at
+ * k = 16 jj + 4 (lane >> 4) + c, tap k / C, channel k % C (zero behind the last tap and in conv1's fourth channel).  Forward: n = co,
+ * C = Cin (4 for conv1), tap = ky KS + kx.  Transposed (the data gradient): n = ci, C = Cout, tap = (KS-1-ky) KS + (KS-1-kx). */
+int lz_lpips_pack(const lz_lpips_weights* weights, float* packed, size_t packed_floats);
+/* replaces the activations autograd keeps for lpips.LPIPS(net='alex').forward (TrainerUtil.py:283,309): bytes of device workspace for one
+ * call (0 for an unsupported shape); 16-byte aligned, no initialisation.  lz_lpips_forward fills it, lz_lpips_backward reads the features in
+ * it and uses the rest as gradient buffers, so it lives from the forward to the backward of a call. */
+size_t lz_lpips_workspace_bytes(uint32_t P, uint32_t H, uint32_t W);
+/* replaces lpips.LPIPS(net='alex').forward(pred, target) (TrainerUtil.py:283,309): value [P].  packed: the device copy of lz_lpips_pack's
+ * image.  Nine launches. */
+int lz_lpips_forward(const float* packed, const float* pred, const float* target, uint32_t P, uint32_t H, uint32_t W, void* workspace,
+                     float* value, lz_stream_t stream);
+/* replaces autograd's backward of lpips.LPIPS(net='alex').forward (TrainerUtil.py:283,309) towards pred: g_pred [P,3,H,W] =
+ * g_value[p] d value[p] / d pred, on the workspace lz_lpips_forward filled for the same P, H, W.  g_value: device f32 [P], read on the
+ * device.  Max-pool ties send the gradient to the first maximum in row-major window order; the ReLU backward is a select (f > 0 ? g : 0).
+ * Eight launches. */
+int lz_lpips_backward(const float* packed, const float* g_value, uint32_t P, uint32_t H, uint32_t W, void* workspace, float* g_pred,
+                      lz_stream_t stream);
 
 #ifdef __cplusplus
 }

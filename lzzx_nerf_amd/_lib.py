@@ -97,6 +97,11 @@ class FrameNgp(C.Structure):
                 ("T_thresh", f32), ("sample_budget", u32), ("n_step_cap", u32)]
 
 
+class LpipsWeights(C.Structure):
+    """mirror of lz_lpips_weights (include/lzzx_nerf_hip.h); HOST pointers"""
+    _fields_ = [("conv_w", vp * 5), ("conv_b", vp * 5), ("lin_w", vp * 5), ("shift", f32 * 3), ("scale", f32 * 3)]
+
+
 # name -> argtypes, in the order of include/lzzx_nerf_hip.h
 SIGNATURES = {
     "lz_grid_encode_forward": [vp, vp, vp, vp, u32, u32, u32, u32, f32, u32, vp, u32, i32, i32, i32, vp],
@@ -225,6 +230,11 @@ SIGNATURES = {
     "lz_objective_torso_backward": [vp, vp, vp, vp, u32, u32, vp, vp, vp],
     "lz_objective_jitter_forward": [vp] * 6 + [u32, u32, f32, vp, vp, vp, vp],
     "lz_objective_jitter_backward": [vp] * 7 + [u32, u32, f32, vp, vp, vp, vp],
+    "lz_objective_pred_backward": [vp, vp, vp, vp, u32, f32, u32, vp, vp, vp],
+    # the perceptual loss (csrc/lz_lpips.hip, lzzx_nerf_amd/perceptual.py)
+    "lz_lpips_pack": [C.POINTER(LpipsWeights), vp, C.c_size_t],
+    "lz_lpips_forward": [vp, vp, vp, u32, u32, u32, vp, vp, vp],
+    "lz_lpips_backward": [vp, vp, u32, u32, u32, vp, vp, vp],
 }
 LZ_OBJECTIVE_WS_BYTES = 64 + 2048 * 8 * 8   # include/lzzx_nerf_hip.h
 LZ_OBJ_UNC, LZ_OBJ_AMB_AUD, LZ_OBJ_AMB_EYE = 1, 2, 4
@@ -233,7 +243,8 @@ PLAIN = {"lz_last_error": ([], C.c_char_p), "lz_abi_version": ([], i32), "lz_dev
          "lz_head_packed_size": ([], u32), "lz_head_packed_size_f16": ([], u32), "lz_head_packed_size_f16w": ([], u32), "lz_head_packed_unc_size_f16": ([], u32), "lz_head_packed_bwd_size_f16": ([], u32),
          "lz_triplane_head_grad_w_workspace": ([], C.c_size_t), "lz_torso_train_workspace": ([], C.c_size_t),
          "lz_audio_train_workspace": ([], C.c_size_t), "lz_audio_track_workspace": ([u32, u32, u32], C.c_size_t), "lz_ngp_train_workspace": ([], C.c_size_t),
-         "lz_mc_workspace": ([u32, u32, u32], C.c_size_t), "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t)}
+         "lz_mc_workspace": ([u32, u32, u32], C.c_size_t), "lz_grid_ordered_workspace": ([u32, u32], C.c_size_t), "lz_grid_fixed_workspace": ([u32, u32], C.c_size_t),
+         "lz_lpips_packed_floats": ([], C.c_size_t), "lz_lpips_workspace_bytes": ([u32, u32, u32], C.c_size_t)}
 
 ALL_SYMBOLS = sorted(list(SIGNATURES) + list(PLAIN))
 ABI_VERSION = 11  # lz_abi_version() of the library this binding table describes (include/lzzx_nerf_hip.h)

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 SO = os.path.join(LIBDIR, "liblzzx_nerf_hip.so")
-SOURCES = ["lz_grid.hip", "lz_grid_fixed.hip", "lz_triplane_enc.hip", "lz_encoders.hip", "lz_raymarch.hip", "lz_head.hip", "lz_head_rec.hip", "lz_head_rec16.hip", "lz_head_gradw.hip", "lz_head_f16.hip", "lz_density.hip", "lz_mesh.hip", "lz_frame.hip", "lz_ngp.hip", "lz_ngp_frame.hip", "lz_ngp_frame_spp.hip", "lz_render.hip", "lz_linear.hip", "lz_torso.hip", "lz_audio.hip", "lz_objective.hip", "lz_torso_train.hip", "lz_audio_train.hip", "lz_ngp_train.hip"]
+SOURCES = ["lz_grid.hip", "lz_grid_fixed.hip", "lz_triplane_enc.hip", "lz_encoders.hip", "lz_raymarch.hip", "lz_head.hip", "lz_head_rec.hip", "lz_head_rec16.hip", "lz_head_gradw.hip", "lz_head_f16.hip", "lz_density.hip", "lz_mesh.hip", "lz_frame.hip", "lz_ngp.hip", "lz_ngp_frame.hip", "lz_ngp_frame_spp.hip", "lz_render.hip", "lz_linear.hip", "lz_torso.hip", "lz_audio.hip", "lz_objective.hip", "lz_lpips.hip", "lz_torso_train.hip", "lz_audio_train.hip", "lz_ngp_train.hip"]
 # -ffp-contract=off: every FMA in the kernels is explicit, so results are bit-identical to the CPU checker
 # No fast-math, and hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt must stay on: a device-side `1.0f / x` has to be the IEEE quotient
 # the host forms -- lz_head_map01 (lz_head_gather.h) forms 1 / (2 bound) on the device when 2 bound is no power of two, every other kernel takes

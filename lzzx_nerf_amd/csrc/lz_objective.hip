@@ -324,6 +324,37 @@ extern "C" int lz_objective_head_backward(const float* grad_loss, const float* i
     return LZ_OK;
 }
 
+// pred's own gradient (a loss term that reads pred, the LPIPS terms): back through the clamp and the blend, in lzo_ray's arithmetic
+__global__ void __launch_bounds__(LZO_THREADS) lz_k_obj_pred_backward(const float* __restrict__ g_pred, const float* __restrict__ image,
+                                                                     const float* __restrict__ ws, const float* __restrict__ bg, uint32_t bg_mode,
+                                                                     float bg_scalar, uint32_t N, float* __restrict__ g_image, float* __restrict__ g_ws) {
+    const uint32_t i = blockIdx.x * LZO_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const float one_m_ws = 1.0f - ws[i];
+    float acc = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float b = bg_mode == 0 ? bg_scalar : (bg_mode == 1 ? bg[0] : (bg_mode == 2 ? bg[c] : bg[(size_t)i * 3 + c]));
+        const float v = image[(size_t)i * 3 + c] + one_m_ws * b;
+        const float gv = (v >= 0.0f && v <= 1.0f) ? g_pred[(size_t)i * 3 + c] : 0.0f;    // clamp(0, 1): passes where 0 <= v <= 1
+        g_image[(size_t)i * 3 + c] = gv;
+        acc -= gv * b;
+    }
+    g_ws[i] = acc;
+}
+
+extern "C" int lz_objective_pred_backward(const float* g_pred, const float* image_raw, const float* weights_sum, const float* bg, uint32_t bg_mode,
+                                          float bg_scalar, uint32_t N, float* g_image_raw, float* g_weights_sum, lz_stream_t stream) {
+    if (N == 0) return LZ_OK;
+    LZ_REQUIRE(g_pred && image_raw && weights_sum && g_image_raw && g_weights_sum, LZ_ERR_BAD_ARGUMENT, "objective_pred_backward: null tensor");
+    LZ_REQUIRE(bg_mode <= 3 && (bg_mode == 0 || bg), LZ_ERR_BAD_ARGUMENT, "objective_pred_backward: bg_mode %u (0 scalar, 1 [1], 2 [3], 3 [N,3]) or null bg",
+               bg_mode);
+    hipLaunchKernelGGL(lz_k_obj_pred_backward, dim3(lz_div_up(N, LZO_THREADS)), dim3(LZO_THREADS), 0, lz_st(stream), g_pred, image_raw, weights_sum, bg,
+                       bg_mode, bg_scalar, N, g_image_raw, g_weights_sum);
+    LZ_CHECK_LAUNCH("objective_pred_backward");
+    return LZ_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // torso (TrainerUtil.py:238-244): mean_i mean_c (C - T)^2 + mean_j (1 - anchor[j, 3])^2
 // ---------------------------------------------------------------------------------------------------------------------------------

@@ -9,8 +9,13 @@ csrc/lz_objective.hip, as autograd Functions:
 
 The head objective is two launches forward (one without unc_loss) and one backward; each of the others one and one.  No host
 synchronisation: the upstream gradient (1, or a GradScaler's scale) is read on the device.  All inputs are f32 (under autocast they are
-cast to f32, as the reference's are: every input of its objective is f32).  Out of scope, as in the rest of the package: LPIPS
-(patch_size > 1, finetune_lips) and color_space 'linear' (convert the target first)."""
+cast to f32, as the reference's are: every input of its objective is f32).
+
+The two LPIPS branches of train_step (:274-284 for patch_size > 1, :291-309 for finetune_lips) run when HeadObjective is given a
+perceptual.FusedLPIPS (`lpips=`): the term is computed on pred_rgb, in f32 (the reference runs it under autocast), and its gradient
+reaches image_raw and weights_sum through the clamp by lz_objective_pred_backward; `terms` then has a seventh element, the LPIPS term as
+it enters the loss.  Without `lpips` both options are rejected, as before.  Out of scope, as in the rest of the package: color_space
+'linear' (convert the target first) and the LPIPS / LMD meters."""
 import torch
 from torch.autograd import Function
 
@@ -88,14 +93,48 @@ class _HeadObjective(Function):
         return (g_img, g_ws, g_aud, g_eye, g_unc) + (None,) * 9
 
 
+class _PredRGB(Function):
+    """pred_rgb of _HeadObjective made differentiable: the same values, and the gradient back through the clamp and the blend"""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, pred, image, ws, bg_mode, bg_scalar, bg):
+        ctx.save_for_backward(image, ws, bg)
+        ctx.args = (bg_mode, bg_scalar)
+        return pred.view_as(pred)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_pred):
+        image, ws, bg = ctx.saved_tensors
+        bg_mode, bg_scalar = ctx.args
+        g = g_pred.float().contiguous()
+        g_img, g_ws = torch.empty_like(image), torch.empty_like(ws)
+        call("lz_objective_pred_backward", ptr(g), ptr(image), ptr(ws), ptr(bg), bg_mode, bg_scalar, ws.shape[0], ptr(g_img), ptr(g_ws), stream())
+        return None, g_img, g_ws, None, None, None
+
+
+LPIPS_PATCH_WEIGHT, LPIPS_LIPS_WEIGHT, LPIPS_LIPS_MIN = 0.1, 0.01, 32      # TrainerUtil.py:284, :309, :298-299
+
+
 class HeadObjective:
-    """TrainerUtil.train_step for the head (opt.torso off, B == 1, patch_size 1, finetune_lips off); defaults of train.py:28,35,48-51.
-    amb_eye_loss without amb_aud_loss is rejected: the reference's eye term reads the audio term's lambda and input (a NameError there)."""
+    """TrainerUtil.train_step for the head (opt.torso off, B == 1); defaults of train.py:28,35,48-51.
+    amb_eye_loss without amb_aud_loss is rejected: the reference's eye term reads the audio term's lambda and input (a NameError there).
+
+    lpips: a perceptual.FusedLPIPS, needed for patch_size > 1 and finetune_lips (a ValueError without it).  patch_size > 1 adds
+    0.1 * mean_p LPIPS over the rays viewed as [-1, ps, ps, 3] (:275-284; N a multiple of ps^2, ps >= 31).  finetune_lips makes __call__
+    accept rect=(xmin, xmax, ymin, ymax): on a step that gives it, 0.01 * LPIPS of the view [1, xmax-xmin, ymax-ymin, 3], scaled to
+    [-1, 1] and then zero-padded symmetrically to at least 32 (:295-303; N must equal the rectangle's area), is added; with rect=None the
+    term is absent and the step is today's objective bit for bit -- the caller alternates, as the reference flips opt.finetune_lips.
+    unc_loss=False gives the reference's arrangement while flip_finetune_lips is on."""
 
     def __init__(self, iters, unc_loss=True, amb_aud_loss=True, amb_eye_loss=True, lambda_amb=1e-4, max_steps=16, patch_size=1,
-                 finetune_lips=False):
-        if patch_size > 1 or finetune_lips:
-            raise ValueError("the LPIPS terms (patch_size > 1, finetune_lips) are not implemented")
+                 finetune_lips=False, lpips=None):
+        if (patch_size > 1 or finetune_lips) and lpips is None:
+            raise ValueError("the LPIPS terms (patch_size > 1, finetune_lips) are not implemented without lpips= (a perceptual.FusedLPIPS)")
+        if patch_size > 1 and patch_size < 31:
+            raise ValueError(f"patch_size {patch_size}: the LPIPS trunk needs patches of at least 31 x 31")
+        self.lpips, self.patch_size, self.finetune_lips = lpips, int(patch_size), bool(finetune_lips)
         if amb_eye_loss and not amb_aud_loss:
             raise ValueError("amb_eye_loss needs amb_aud_loss (the reference's eye term uses its lambda and ambient_aud)")
         if iters <= 0:
@@ -115,11 +154,25 @@ class HeadObjective:
     def wants_regularizer(global_step):
         return global_step % 16 == 0
 
-    def __call__(self, image_raw, weights_sum, amb_aud_sum, amb_eye_sum, uncertainty_sum, bg_color, target, face_mask, global_step):
+    def __call__(self, image_raw, weights_sum, amb_aud_sum, amb_eye_sum, uncertainty_sum, bg_color, target, face_mask, global_step, rect=None):
         ws = _rays(weights_sum, "weights_sum", None)
         N = ws.shape[0]
         if N == 0:
             raise ValueError("no rays (N = 0)")
+        if rect is not None and not self.finetune_lips:
+            raise ValueError("rect is the lips rectangle of finetune_lips=True")
+        views = []      # (coefficient, image height, image width, pad to 32) of the LPIPS terms of this step
+        if self.patch_size > 1:
+            ps = self.patch_size
+            if N % (ps * ps):
+                raise ValueError(f"{N} rays are no multiple of patch_size^2 = {ps * ps}")
+            views.append((LPIPS_PATCH_WEIGHT, ps, ps, False))
+        if rect is not None:
+            xmin, xmax, ymin, ymax = (int(v) for v in rect)
+            h, w = xmax - xmin, ymax - ymin
+            if h <= 0 or w <= 0 or h * w != N:
+                raise ValueError(f"rect {tuple(rect)} holds {max(h, 0)} x {max(w, 0)} rays, N = {N}")
+            views.append((LPIPS_LIPS_WEIGHT, h, w, True))
         image = _rays(image_raw, "image_raw", 3)
         tgt = _rays(target, "target", 3)
         if not isinstance(face_mask, torch.Tensor) or face_mask.dtype not in (torch.bool, torch.uint8):
@@ -139,6 +192,24 @@ class HeadObjective:
         loss, pred, terms = _HeadObjective.apply(_flat(image_raw, 3), _flat(weights_sum, None), _flat_opt(amb_aud_sum), _flat_opt(amb_eye_sum),
                                                  _flat_opt(uncertainty_sum), tgt, face, bg_mode, bg_scalar, bg, self.flags, sf,
                                                  self.lambda_amb, self.max_steps)
+        if views:
+            # the reference's expressions on pred_rgb and rgb (:275-277, :295-303); the clamp's and the blend's backward is _PredRGB's
+            pred_d = _PredRGB.apply(pred, _flat(image_raw, 3), _flat(weights_sum, None), bg_mode, bg_scalar, bg)
+            extra = None
+            for coef, h, w, pad in views:
+                a = pred_d.view(-1, h, w, 3).permute(0, 3, 1, 2).contiguous() * 2 - 1
+                b = tgt.detach().view(-1, h, w, 3).permute(0, 3, 1, 2).contiguous() * 2 - 1
+                if pad:
+                    pad_h, pad_w = max(0, (LPIPS_LIPS_MIN - h + 1) // 2), max(0, (LPIPS_LIPS_MIN - w + 1) // 2)
+                    if pad_h or pad_w:
+                        a = torch.nn.functional.pad(a, (pad_w, pad_w, pad_h, pad_h))
+                        b = torch.nn.functional.pad(b, (pad_w, pad_w, pad_h, pad_h))
+                term = coef * self.lpips(a, b).mean()
+                extra = term if extra is None else extra + term
+            loss = loss + extra
+            terms = torch.cat([terms, extra.detach().reshape(1)])
+        elif self.lpips is not None:
+            terms = torch.cat([terms, terms.new_zeros(1)])
         return loss, pred.view(image_raw.shape), terms
 
 

@@ -138,3 +138,18 @@ class GenericHashgridNeRF:
                 rows += n_alive * n_step
                 iters += 1
             return torch.clamp(img + (1 - ws)[:, None], 0, 1), dep, ws, rows, iters
+
+
+def lpips_alex_state(seed=0):
+    """Seeded stand-in weights in the key layout of lpips.LPIPS(net='alex').state_dict() (perceptual.py), as f32 numpy arrays, for the
+    tests and benchmarks -- the published weights cannot be fetched where this project is built.  Convolutions He-scaled normal
+    (std sqrt(2 / fan_in)), biases 0.1 * normal, lin weights uniform in [0, 1); scaling_layer holds the published constants."""
+    from .perceptual import CONV_KEYS, CONV_SHAPES, SCALE, SHIFT
+    rng = np.random.default_rng(seed)
+    sd = {"scaling_layer.shift": np.array(SHIFT, np.float32).reshape(1, 3, 1, 1), "scaling_layer.scale": np.array(SCALE, np.float32).reshape(1, 3, 1, 1)}
+    for i, (key, shape) in enumerate(zip(CONV_KEYS, CONV_SHAPES)):
+        fan_in = shape[1] * shape[2] * shape[3]
+        sd[key + ".weight"] = (rng.standard_normal(shape) * np.sqrt(2.0 / fan_in)).astype(np.float32)
+        sd[key + ".bias"] = (0.1 * rng.standard_normal(shape[0])).astype(np.float32)
+        sd[f"lin{i}.model.1.weight"] = rng.random((1, shape[0], 1, 1)).astype(np.float32)
+    return sd
